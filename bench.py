@@ -15,7 +15,11 @@ environment starts the N ranks itself (torch.distributed.run as a child process,
 touches the GPU); under torchrun WORLD_SIZE must equal --gpus.  Rank 0 limb-checks every rank's
 gathered output of the last timed step against the oracle digest of that rank's workload.
 
-Prints ONE JSON line on rank 0.  `roofline` is for the kernel that the newest hash-matched rocprofv3
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`, the sorted step times); `--dump-outputs DIR` also writes the last timed step's output
+limbs as DIR/*.npy (dump_outputs).  Everything below is measured only with `--full` (the instrumented
+per-kernel pass, the digest checks, the sustained run, the SEAL, block and cfg5 legs, the CPU baselines).
+With `--full`, `roofline` is for the kernel that the newest hash-matched rocprofv3
 record of this workload (profiles/r*/rocprof_summary_<config>.json, tools/rocprof_summary.py) shows
 with the longest steady-state device time per step, measured live in the timed region with HIP events
 on the library stream around its launches; `cpu_baseline` times full
@@ -201,6 +205,33 @@ def limb_digest_check(config, limbs, suffix=""):
             "source": "tests/golden/manifest.json bench_digests (C oracle, tests/golden/make_bench_digest.py)"}
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: every array of `arrays` as DIR/<name>.npy in float64, so that two builds run with the same
+    arguments can be compared output for output.  uint64 limbs (up to 59 bits: not exact in float64) are written
+    as their two 32-bit halves, <name>_lo.npy and <name>_hi.npy (value = hi * 2**32 + lo), both exact.  All
+    files together stay under 64 MB: an array over its share is written as a fixed sample of its flattened
+    elements (indices from numpy's default_rng(0), sorted), the same sample in every run."""
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.uint64:
+            files[name + "_lo"] = (a & np.uint64(0xFFFFFFFF)).astype(np.float64)
+            files[name + "_hi"] = (a >> np.uint64(32)).astype(np.float64)
+        else:
+            files[name] = a.astype(np.float64)
+    share = DUMP_MAX_BYTES // max(1, len(files)) // 8 - 16      # elements per file (the .npy header is 128 bytes)
+    for name, a in files.items():
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(out / f"{name}.npy", a)
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -306,6 +337,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)   # median of 20 after 3 warmups
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg2", choices=sorted(k for k in CONFIGS if k != "block_small"))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline's timed steps: the instrumented per-kernel pass and rooflines, the limb "
+                         "checks against the oracle digests, the sustained run, the SEAL-convention, RWKV-block and "
+                         "cfg5 legs and the CPU baselines (each with its --no-* switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-reps", type=int, default=3, help="timed full CPU matvecs (after one untimed)")
     ap.add_argument("--no-block", action="store_true",
@@ -397,12 +434,12 @@ def main():
 
     mv = leg("matvec", matvec_leg, args, ph, dist, tdist, rank, world, local, ident)
     seal = None
-    if world == 1 and args.config == "cfg2" and not args.no_seal:
+    if args.full and world == 1 and args.config == "cfg2" and not args.no_seal:
         # north_star's bit-exact claim is stated against SEAL's switch_key_inplace convention: the same
         # matvec in that mode (P = 1, dnum = L0, the baby rotations hoisted and corrected to SEAL's lift)
         seal = leg("seal", seal_leg, args, ph, cfg)
     block = None
-    if not args.no_block and args.config == "cfg2":
+    if args.full and not args.no_block and args.config == "cfg2":
         # the metric's second half, measured: one client-aided RWKV-7 block (cfg3 shapes) on the same
         # ranks, after the matvec leg's memory is released
         block = leg("block", run_block, args, ph, tdist, rank, world, local, args.block_steps, 1,
@@ -415,7 +452,7 @@ def main():
             if rank == 0 and isinstance(block, dict):
                 block["baby_broadcast"] = bb if bb is not None else leg_error(faults["block_broadcast"])
     cfg5 = None
-    if not args.no_cfg5 and args.config == "cfg2":
+    if args.full and not args.no_cfg5 and args.config == "cfg2":
         cfg5 = leg("cfg5", run_cfg5, args, ph, tdist, rank, world, local)
     if rank == 0:
         try:
@@ -434,8 +471,8 @@ def main():
 
 def matvec_leg(args, ph, dist, tdist, rank, world, local, ident):
     """The headline leg: K timed BSGS matvecs of `args.config` (one per rank per step, outputs gathered to rank 0
-    at N > 1), the instrumented per-kernel pass before them, the sustained sub-leg after them (world 1), and the
-    limb checks.  Returns what the line needs (rank 0; the timing reductions run on every rank)."""
+    at N > 1) and, with --full, the instrumented per-kernel pass before them, the sustained sub-leg after them
+    (world 1), and the limb checks.  Returns what the line needs (rank 0; the timing reductions run on every rank)."""
     cfg = CONFIGS[args.config]
     N, L0, P, D = cfg["N"], cfg["L0"], cfg["P"], cfg["D"]
     G, B = bsgs_params(D)
@@ -505,28 +542,30 @@ def matvec_leg(args, ph, dist, tdist, rank, world, local, ident):
             import torch
             torch.cuda.synchronize()
 
-    # per-kernel breakdown from an instrumented, untimed pass (every kernel bracketed by HIP events)
-    prof_steps = max(1, min(3, args.steps))
-    ph.kernel_timer_read(ctx, reset=True)
-    ph.kernel_timer_arm(ctx, None)
-    for _ in range(prof_steps):
-        step()
-    ctx.synchronize()
-    kprof = ph.kernel_timer_read(ctx, reset=True)
-    # the roofline kernel, by a fixed rule: the priced kernel (one with algorithmic bytes) with the
-    # longest steady-state device time per step in the newest rocprofv3 record of this workload whose
-    # kernel-source hash matches these sources (tools/rocprof_summary.py); without such a record, the
-    # longest priced kernel of the instrumented pass above
-    rrec, rsrc = latest_record("rocprof_summary", args.config)
-    priced = [k for k in kprof if kprof[k][1] and algorithmic_bytes_per_matvec(k, cfg, L0 + 1 - level)]
-    if rrec and rrec.get("longest_matvec_kernel") in priced:
-        dom, dom_rule = rrec["longest_matvec_kernel"], f"longest priced kernel per step in {rsrc} (rocprofv3)"
-    else:
-        dom = max(priced or list(kprof), key=lambda k: kprof[k][0])
-        dom_rule = "longest priced kernel of this run's instrumented pass (no hash-matched rocprof record)"
-    # timed region: the ModUp and Hadamard kernels (and the dominant one) carry events, measured live on
-    # the context stream they launch on (each event pair costs ~10 us of queue time)
-    ph.kernel_timer_arm(ctx, sorted({dom, "k_modup", "k_bsgs_inner"}))
+    kprof = prof_steps = dom = dom_rule = rrec = None
+    if args.full:
+        # per-kernel breakdown from an instrumented, untimed pass (every kernel bracketed by HIP events)
+        prof_steps = max(1, min(3, args.steps))
+        ph.kernel_timer_read(ctx, reset=True)
+        ph.kernel_timer_arm(ctx, None)
+        for _ in range(prof_steps):
+            step()
+        ctx.synchronize()
+        kprof = ph.kernel_timer_read(ctx, reset=True)
+        # the roofline kernel, by a fixed rule: the priced kernel (one with algorithmic bytes) with the
+        # longest steady-state device time per step in the newest rocprofv3 record of this workload whose
+        # kernel-source hash matches these sources (tools/rocprof_summary.py); without such a record, the
+        # longest priced kernel of the instrumented pass above
+        rrec, rsrc = latest_record("rocprof_summary", args.config)
+        priced = [k for k in kprof if kprof[k][1] and algorithmic_bytes_per_matvec(k, cfg, L0 + 1 - level)]
+        if rrec and rrec.get("longest_matvec_kernel") in priced:
+            dom, dom_rule = rrec["longest_matvec_kernel"], f"longest priced kernel per step in {rsrc} (rocprofv3)"
+        else:
+            dom = max(priced or list(kprof), key=lambda k: kprof[k][0])
+            dom_rule = "longest priced kernel of this run's instrumented pass (no hash-matched rocprof record)"
+        # timed region: the ModUp and Hadamard kernels (and the dominant one) carry events, measured live on
+        # the context stream they launch on (each event pair costs ~10 us of queue time)
+        ph.kernel_timer_arm(ctx, sorted({dom, "k_modup", "k_bsgs_inner"}))
     barrier()
     ctx.synchronize()
     if tdist is not None:
@@ -549,8 +588,10 @@ def matvec_leg(args, ph, dist, tdist, rank, world, local, ident):
     step_ms = sorted(a.elapsed_ms(b) for a, b in evs)
     median_ms = float(np.median(step_ms))
     del evs
-    ktimes = ph.kernel_timer_read(ctx, reset=True)
-    ph.kernel_timer_arm(ctx, [])
+    ktimes = None
+    if args.full:
+        ktimes = ph.kernel_timer_read(ctx, reset=True)
+        ph.kernel_timer_arm(ctx, [])
     # the pinned descriptor ring's segment re-entries so far, and how many had to wait for the GPU (a wait
     # drains the queue: the r03 host stall's candidate cause, now event-gated per segment)
     staging = dict(zip(("segment_reentries", "reentries_that_waited"), ph.staging_stats(ctx)))
@@ -566,9 +607,12 @@ def matvec_leg(args, ph, dist, tdist, rank, world, local, ident):
     # correctness guard on the timed output: the level, and on rank 0 the SHA-256 of its limbs against
     # the digest the C oracle computed for this exact workload (tests/golden/manifest.json)
     assert y.chain_index() == level + 1
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last timed step: the output ciphertext's limbs
+        dump_outputs(args.dump_outputs, {"y_limbs": y.to_numpy()})
     dkey = cfg.get("digest", args.config)
-    parity = limb_digest_check(dkey, y.to_numpy()) if rank == 0 else None
-    if dist is not None and rank == 0:
+    parity = limb_digest_check(dkey, y.to_numpy()) if rank == 0 and args.full else None
+    if dist is not None and rank == 0 and args.full:
         # every rank's output of the last timed step, as gathered over RCCL (gloo in rehearsals), against
         # the oracle digest of that rank's workload (seeds + rank, tests/golden/make_bench_digest.py --rank)
         shape = (2, L0 - 1, N)
@@ -581,7 +625,7 @@ def matvec_leg(args, ph, dist, tdist, rank, world, local, ident):
                                       "all_match": all(v[k] is True for v, k in zip(per.values(), keys)),
                                       "per_rank": {r: v[k] for (r, v), k in zip(per.items(), keys)}}
     sustained = None
-    if world == 1 and args.sustain_s > 0:
+    if args.full and world == 1 and args.sustain_s > 0:
         phase(f"{args.config} sustained")
         sustained = sustained_run(args, ph, ctx, step, dom, cfg, L0 + 1 - level, ident, dkey)
     del pts, ct, y, gk, sk, pt_x
@@ -659,6 +703,25 @@ def build_line(args, cfg, mv, seal, block, cfg5, faults, ranks_rec, world):
                       "rotations_per_matvec": (G - 1) + (B - 1), "projections_per_rank": 1,
                       "parallelism": f"projection-parallel x{world}" + (" + RCCL gather" if world > 1 else "")}}
     l = None
+    if not args.full:
+        # the plain line: the headline of the timed steps alone (everything below is the --full line)
+        res["full"] = False
+        if mv is not None:
+            median_ms, elapsed = mv["median_ms"], mv["elapsed"]
+            mean_value = args.steps * world / elapsed
+            res.update({"value": round(1000.0 * world / median_ms if world == 1 else mean_value, 3),
+                        "ms_per_step": round(1000.0 * elapsed / args.steps, 3),
+                        "median_ms_per_step": round(median_ms, 3),
+                        "value_basis": ("median of the K steps' HIP-event device times" if world == 1 else
+                                        "K x N matvecs / wall time of the K steps (max over ranks)"),
+                        "mean_value": round(mean_value, 3), "step_ms_sorted": mv["step_ms"],
+                        "staging_ring": mv["staging"], "exchange_per_step": mv["exchange"]})
+        else:
+            res["error"] = leg_error(faults["matvec"])
+        res["ranks"] = ranks_rec
+        res["leg_faults"] = faults
+        return res
+    res["full"] = True
     if mv is not None:
         level, kprof, prof_steps, ktimes = mv["level"], mv["kprof"], mv["prof_steps"], mv["ktimes"]
         median_ms, elapsed, dom, rrec = mv["median_ms"], mv["elapsed"], mv["dom"], mv["rrec"]
@@ -1159,6 +1222,9 @@ def bench_block(args, ph, dist, rank, world, local):
         err = float(np.max(np.abs(out[0] - ref[0])))
         if not err < 1e-6 * max(1.0, float(np.max(np.abs(ref[0])))):
             raise AssertionError(f"bench cfg3: decrypted block output off the plaintext block by {err:.3e}")
+        if args.dump_outputs:
+            # the client's decrypted results of the last timed block (tools/rwkv_block.py client_aided_block)
+            dump_outputs(args.dump_outputs, dict(zip(("x", "x_ln", "x_ffn_ln", "state", "v_first"), out[:5])))
         sec = elapsed / args.steps
         l = cfg["L0"]
         mv = matvec_bytes(dict(cfg), l)

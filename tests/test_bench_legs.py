@@ -27,3 +27,38 @@ def test_block_leg_with_cpu_limb_check(require_gpu):
     assert cap["ct_in"].shape == (2, 6, 4096) and cap["ct_out"].shape == (2, 5, 4096) and len(cap["pts"]) == 64
     par = bench.cpu_check_block_projection(cap)
     assert par["r_projection_limbs_match_cpu_port"], par
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_oracle_limbs(require_gpu, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full at the smoke size (N=4096, L0=6, D=256):
+    K timed steps, ms_per_step consistent with them, none of the --full records, and the dumped limbs of the
+    last timed step (two exact float64 halves) hash to the C oracle's digest of this workload
+    (tests/golden/manifest.json bench_digests.small)."""
+    import hashlib
+    import json
+    import subprocess
+
+    import numpy as np
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--config", "small", "--dump-outputs", str(tmp_path)], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and len(res["step_ms_sorted"]) == 3 and res["full"] is False
+    assert res["unit"] == "matvec/s" and res["higher_is_better"] is True and res["dtype"] == "u64"
+    # value = 1000 / median step ms; the line rounds both to 3 decimals (the median is a fraction of a ms here)
+    m = res["median_ms_per_step"]
+    assert 1000.0 / (m + 0.0005) - 0.001 <= res["value"] <= 1000.0 / (m - 0.0005) + 0.001
+    # the wall time of the K steps brackets their device times (same stream, one after the other)
+    assert res["ms_per_step"] * 3 >= 0.9 * sum(res["step_ms_sorted"])
+    assert not {"roofline", "kernels", "cpu_baseline", "parity", "sustained", "seal_mode", "rwkv_block",
+                "cfg5_chain"} & set(res)
+    assert sorted(f.name for f in tmp_path.iterdir()) == ["y_limbs_hi.npy", "y_limbs_lo.npy"]
+    hi, lo = np.load(tmp_path / "y_limbs_hi.npy"), np.load(tmp_path / "y_limbs_lo.npy")
+    assert hi.dtype == lo.dtype == np.float64 and hi.shape == lo.shape == (2, 5, 4096)
+    limbs = hi.astype(np.uint64) * np.uint64(2 ** 32) + lo.astype(np.uint64)
+    want = json.loads((REPO / "tests" / "golden" / "manifest.json").read_text())["bench_digests"]["small"]["sha256"]
+    assert hashlib.sha256(limbs.tobytes()).hexdigest() == want

@@ -3,8 +3,8 @@
 tests/_fence_worker.py runs three legs shaped like bench.py's N > 1 legs (a gathered matvec loop, the RWKV block's
 dependent broadcast / point-to-point stages, the cfg5 chain's flag broadcast / reduce / barrier blocks) through
 fhespear_dist.FailureFence + TimedDist, as bench.py does; FHESPEAR_BENCH_INJECT raises on one rank at a leg's start
-or at a stage boundary while its peers wait in collectives on it.  Every configuration runs at once (distinct
-ports) so the suite pays for one rendezvous."""
+or at a stage boundary while its peers wait in collectives on it.  The configurations run side by side
+(distinct ports) in three groups of at most MAX_PROCS processes, so the suite pays for three rendezvous."""
 import json
 import os
 import socket
@@ -40,28 +40,53 @@ def _port():
         return s.getsockname()[1]
 
 
+# Processes alive at once, launchers included (a configuration costs world + 1).  On a GPU host every process that
+# imports torch may hold the device open, and hosts bound how many may: 14 plus the test runner stays under 16.
+MAX_PROCS = 14
+
+
+def _batches():
+    """CASES' indices packed into as few groups of at most MAX_PROCS processes as first-fit, largest first, gives."""
+    groups = []
+    for k in sorted(range(len(CASES)), key=lambda k: -CASES[k][0]):
+        cost = CASES[k][0] + 1
+        g = next((g for g in groups if sum(CASES[j][0] + 1 for j in g) + cost <= MAX_PROCS), None)
+        if g is None:
+            groups.append([k])
+        else:
+            g.append(k)
+    return groups
+
+
+def _start(world, inj, reinit):
+    env = dict(os.environ, FHESPEAR_BENCH_INJECT="" if inj.startswith("hang:") else inj,
+               FENCE_HANG=inj[5:] if inj.startswith("hang:") else "", FHESPEAR_LEG_TIMEOUT="3",
+               FENCE_REINIT="1" if reinit else "0", OMP_NUM_THREADS="1", MASTER_ADDR="127.0.0.1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
+           "--master-addr=127.0.0.1", f"--master-port={_port()}", str(WORKER)]
+    return time.time(), subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+
+
 @pytest.fixture(scope="module")
 def runs():
-    procs = []
-    for world, inj, reinit in CASES:
-        env = dict(os.environ, FHESPEAR_BENCH_INJECT="" if inj.startswith("hang:") else inj,
-                   FENCE_HANG=inj[5:] if inj.startswith("hang:") else "", FHESPEAR_LEG_TIMEOUT="3",
-                   FENCE_REINIT="1" if reinit else "0", OMP_NUM_THREADS="1", MASTER_ADDR="127.0.0.1")
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-               "--master-addr=127.0.0.1", f"--master-port={_port()}", str(WORKER)]
-        procs.append((time.time(), subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                                                    text=True)))
-    out = []
-    for (world, inj, reinit), (t0, p) in zip(CASES, procs):
-        try:
-            so, se = p.communicate(timeout=180)
-        except subprocess.TimeoutExpired:
-            p.kill()
-            so, se = p.communicate()
-            pytest.fail(f"world {world} inject {inj!r}: hung\n{se[-3000:]}")
-        line = [ln for ln in so.splitlines() if ln.startswith("{")]
-        out.append(dict(world=world, inj=inj, reinit=reinit, rc=p.returncode, line=json.loads(line[-1]) if line else None,
-                        stderr=se, wall=time.time() - t0))
+    out = [None] * len(CASES)
+    for group in _batches():       # the configurations of a group run at once; a group starts when the last has ended
+        procs = [(k, _start(*CASES[k])) for k in group]
+        hung = None
+        for k, (t0, p) in procs:
+            world, inj, reinit = CASES[k]
+            try:
+                so, se = p.communicate(timeout=180)
+            except subprocess.TimeoutExpired:
+                p.kill()
+                so, se = p.communicate()
+                hung = hung or f"world {world} inject {inj!r}: hung\n{se[-3000:]}"
+                continue
+            line = [ln for ln in so.splitlines() if ln.startswith("{")]
+            out[k] = dict(world=world, inj=inj, reinit=reinit, rc=p.returncode,
+                          line=json.loads(line[-1]) if line else None, stderr=se, wall=time.time() - t0)
+        if hung:
+            pytest.fail(hung)
     return out
 
 

@@ -11,15 +11,33 @@ import pytest
 
 REPO = Path(__file__).resolve().parents[1]
 PYDIR = REPO / "fhe-spear_amd" / "python"
-REF_FC = Path("/root/reference/fhe_common.py")
+PATCH = REPO / "integration" / "fhe_common.patch"
 
 
-@pytest.mark.skipif(not REF_FC.is_file(), reason="reference checkout absent (GPU box)")
+def _patch_preimage():
+    """A stand-in for the reference's fhe_common.py, which is not part of this repository: the lines the
+    patch's hunk expects (its context and removed lines, at the hunk's own line number) between a header that
+    imports what they use and a tail that imports pyPhantom and sets USE_PHANTOM_GPU as fc:13-17 does.  Bytes:
+    the reference's file has CRLF line ends, which the hunk's lines carry and patch compares."""
+    lines = PATCH.read_bytes().split(b"\n")
+    at = next(i for i, ln in enumerate(lines) if ln.startswith(b"@@"))
+    start = int(lines[at].split()[1].lstrip(b"-").split(b",")[0])
+    hunk = [ln[1:] for ln in lines[at + 1:] if ln[:1] in (b" ", b"-")]
+    assert hunk and all(ln.endswith(b"\r") for ln in hunk)
+    head = [b"import os\r", b"import sys\r"]
+    head += [b"\r"] * (start - 1 - len(head))
+    tail = [b"try:\r", b"    import pyPhantom\r", b"    USE_PHANTOM_GPU = True\r", b"except ImportError:\r",
+            b"    USE_PHANTOM_GPU = False\r"]
+    return b"\n".join(head + hunk + tail) + b"\n"
+
+
 def test_fhe_common_patch_selects_mi355x_backend(tmp_path):
-    """integration/fhe_common.patch applied to a scratch copy of the reference's fhe_common.py:
+    """integration/fhe_common.patch applied to a stand-in for the reference's fhe_common.py (_patch_preimage):
     with FHESPEAR_PYPHANTOM pointing at fhe-spear_amd/python, `import pyPhantom` inside
     fhe_common resolves to this repo's module and USE_PHANTOM_GPU is True (fc:9-17)."""
-    shutil.copy(REF_FC, tmp_path / "fhe_common.py")
+    if shutil.which("patch") is None:
+        pytest.fail("the patch program is needed to apply integration/fhe_common.patch")
+    (tmp_path / "fhe_common.py").write_bytes(_patch_preimage())
     r = subprocess.run(["patch", "-p1", "-i", str(REPO / "integration" / "fhe_common.patch")], cwd=tmp_path,
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr

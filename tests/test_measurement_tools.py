@@ -181,3 +181,43 @@ def test_multi_rank_line_schema_reports_what_is_missing():
     res["exchange_per_step"]["gather"].pop("ms")
     err = bench.line_schema_errors(res)
     assert len(err) == 3 and any("pci_bus_id" in e for e in err) and any("baby_broadcast" in e for e in err)
+
+
+def test_dump_outputs_is_exact_for_limbs_and_bounded(tmp_path):
+    """--dump-outputs: uint64 limbs come back exactly from their float64 halves; every file is float64; a set of
+    arrays over 64 MB is cut to the same fixed sample in every call."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    limbs = rng.integers(0, 2 ** 59, (2, 5, 1024), dtype=np.uint64)
+    limbs[0, 0, :2] = (2 ** 59 - 1, 2 ** 32)                      # neither survives one float64
+    x = rng.standard_normal(300).astype(np.float32)
+    bench.dump_outputs(tmp_path / "a", {"y_limbs": limbs, "x": x})
+    got = {f.name: np.load(f) for f in sorted((tmp_path / "a").iterdir())}
+    assert sorted(got) == ["x.npy", "y_limbs_hi.npy", "y_limbs_lo.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    back = got["y_limbs_hi.npy"].astype(np.uint64) * np.uint64(2 ** 32) + got["y_limbs_lo.npy"].astype(np.uint64)
+    assert np.array_equal(back, limbs) and np.array_equal(got["x.npy"], x.astype(np.float64))
+    big = np.arange(9_000_000, dtype=np.float64)                  # 72 MB alone
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, {"big": big, "x": x})
+    files = sorted((tmp_path / "b").iterdir())
+    assert sum(f.stat().st_size for f in files) <= 64 * 2 ** 20
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert np.array_equal(b, c) and 4_000_000 < b.size < big.size and np.all(np.diff(b) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "x.npy"), x.astype(np.float64))
+
+
+def test_plain_line_carries_the_headline_only():
+    """Without --full the line is built from the timed steps alone: the contract's fields with their meanings
+    (value = 1000 / median step ms at one rank, ms_per_step = wall time of the K steps / K) and none of the
+    --full records."""
+    import argparse
+    args = argparse.Namespace(full=False, steps=4, warmup=1, config="cfg2", no_cpu_baseline=False)
+    mv = {"median_ms": 6.25, "elapsed": 0.0256, "step_ms": [6.2, 6.2, 6.3, 6.4], "staging": {}, "exchange": None}
+    res = bench.build_line(args, bench.CONFIGS["cfg2"], mv, None, None, None, {}, {"world_size": 1}, 1)
+    assert res["metric"].startswith("BSGS matvecs/sec") and res["unit"] == "matvec/s" and res["dtype"] == "u64"
+    assert res["higher_is_better"] is True and res["steps"] == 4 and res["full"] is False
+    assert res["value"] == 160.0 and res["ms_per_step"] == 6.4
+    assert not {"roofline", "kernels", "cpu_baseline", "parity", "sustained", "seal_mode", "rwkv_block",
+                "cfg5_chain"} & set(res)
+    json.dumps(res)

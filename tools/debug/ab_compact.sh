@@ -14,7 +14,7 @@ for v in "$@"; do
         --timeout-method thread -k "compact or periodic" > "$OUT/test_$v.log" 2>&1 || { tail -30 "$OUT/test_$v.log"; exit 1; }
     echo "$v: $(tail -1 "$OUT/test_$v.log")"
 done
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-seal --sustain-s 0"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-seal --sustain-s 0"
 for rep in 1 2; do
     for v in "$@"; do
         FHESPEAR_LIB=$(lib "$v") timeout -k 10 300 python bench.py $ARGS > "$OUT/bench_${v}_$rep.log" 2>&1 || { tail -30 "$OUT/bench_${v}_$rep.log"; exit 1; }

@@ -8,7 +8,7 @@ set -o pipefail
 OUT=gpurun_out/$1
 mkdir -p "$OUT"
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}" || exit 1
-ARGS="--gpus 1 --steps 5 --warmup 1 --no-cpu-baseline --no-seal --sustain-s 0 --block-steps 1 --cfg5-blocks 2"
+ARGS="--full --gpus 1 --steps 5 --warmup 1 --no-cpu-baseline --no-seal --sustain-s 0 --block-steps 1 --cfg5-blocks 2"
 port=29541
 for inj in "block/stage1@0" "matvec/step2@0"; do
     name=$(echo "$inj" | tr '/@' '__')

@@ -4,9 +4,9 @@
 # Steps, run in order, each under its own time limit; the script stops at the first failure:
 #   tests[=pytest args]     GPU suite (default: all of tests/ -m gpu; args may quote, e.g. -k 'a or b')
 #   smoke                   __graft_entry__.smoke()                              -> OUT/smoke.log
-#   bench[=bench args]      one bench line (default: the driver's default line)  -> OUT/bench.json
+#   bench[=bench args]      one bench line (default: --full, the line with every leg) -> OUT/bench.json
 #   ab=NAME[:ENV=v,ENV=v]   cfg2 matvec-only bench under extra environment (AB_ARGS: more bench args) -> OUT/ab_NAME.json
-#   abx=NAME[:ENV=v,ENV=v]  bench with AB_ARGS only (no matvec-only flags)           -> OUT/ab_NAME.json
+#   abx=NAME[:ENV=v,ENV=v]  bench --full with AB_ARGS only (no matvec-only flags)    -> OUT/ab_NAME.json
 #   trace[=bench args]      rocprofv3 --kernel-trace --stats of a matvec-only bench -> OUT/trace_<config>/,
 #                           OUT/rocprof_summary_<config>.json (tools/rocprof_summary.py: per-dispatch
 #                           steady state of the timed steps)
@@ -14,7 +14,7 @@
 #                           -> OUT/pmc_traffic_<config>.json, OUT/pmc_valu_<config>.json
 #   stall[=config]          wave-cycle attribution passes (SQ_WAIT_*, LDS, instruction mix) -> OUT/pmc_stall_<config>.json
 #   rehearse=N[:bench args] N ranks sharing this one GPU (gloo, host-staged exchange, 2 GiB allocation cache per rank; timings
-#                           meaningless): bench.py --gpus N self-launches them -> OUT/rehearse_nN.json
+#                           meaningless): bench.py --full --gpus N self-launches them -> OUT/rehearse_nN.json
 #   dist1[=NAME[:ENV=v,..]] matvec bench at world 1 under torchrun with the RCCL gather step -> OUT/NAME.json
 #   py=SCRIPT[:args]        python SCRIPT args                                  -> OUT/py_<name>.log
 #   exe=BINARY              a prebuilt microbenchmark                          -> OUT/exe_<name>.log
@@ -25,7 +25,7 @@ OUT=gpurun_out/$1
 shift
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
-MV="--no-cpu-baseline --no-block --no-seal --no-cfg5"
+MV="--full --no-cpu-baseline --no-block --no-seal --no-cfg5"   # the matvec leg alone, with its per-kernel records
 PMV="$MV --sustain-s 0"   # counter passes: the timed steps only (no sustained run under the profiler)
 fail() { echo "step $1 failed"; tail -20 "$2"; exit 1; }
 for step in "$@"; do
@@ -42,7 +42,7 @@ for step in "$@"; do
         timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || fail smoke "$OUT/smoke.log"
         tail -1 "$OUT/smoke.log" ;;
     bench)
-        timeout -k 10 600 python bench.py $arg > "$OUT/bench.log" 2>&1 || fail bench "$OUT/bench.log"
+        timeout -k 10 600 python bench.py ${arg:---full} > "$OUT/bench.log" 2>&1 || fail bench "$OUT/bench.log"
         grep '^{' "$OUT/bench.log" | tail -1 > "$OUT/bench.json"
         python3 tools/show_bench.py "$OUT/bench.json" ;;
     ab)
@@ -57,7 +57,7 @@ for step in "$@"; do
         v=${arg%%:*}
         envs=""
         [ "$v" != "$arg" ] && envs=$(echo "${arg#*:}" | tr ',' ' ')
-        env $envs timeout -k 10 600 python3 bench.py $AB_ARGS > "$OUT/ab_$v.log" 2>&1 || fail "abx $v" "$OUT/ab_$v.log"
+        env $envs timeout -k 10 600 python3 bench.py --full $AB_ARGS > "$OUT/ab_$v.log" 2>&1 || fail "abx $v" "$OUT/ab_$v.log"
         grep '^{' "$OUT/ab_$v.log" | tail -1 > "$OUT/ab_$v.json"
         python3 tools/show_bench.py "$OUT/ab_$v.json" "$v" ;;
     trace)
@@ -130,7 +130,7 @@ for step in "$@"; do
         n=${arg%%:*}
         a=""
         [ "$n" != "$arg" ] && a=${arg#*:}
-        FHESPEAR_DIST_BACKEND=gloo FHESPEAR_DEVICE=0 FHESPEAR_CACHE_BYTES=${FHESPEAR_CACHE_BYTES:-2147483648} timeout -k 10 1100 python bench.py --gpus "$n" $a \
+        FHESPEAR_DIST_BACKEND=gloo FHESPEAR_DEVICE=0 FHESPEAR_CACHE_BYTES=${FHESPEAR_CACHE_BYTES:-2147483648} timeout -k 10 1100 python bench.py --full --gpus "$n" $a \
             > "$OUT/rehearse_n$n.log" 2>&1 || fail "rehearse $n" "$OUT/rehearse_n$n.log"
         grep '^{' "$OUT/rehearse_n$n.log" | tail -1 > "$OUT/rehearse_n$n.json"
         python3 tools/show_bench.py "$OUT/rehearse_n$n.json" ;;
