@@ -380,6 +380,7 @@ struct fhs_ciphertext {
     // the queued rotation that was to produce it could not run (flush failed, e.g. out of memory): its limbs are
     // undefined and every later use fails (drop_pending)
     bool lost = false;
+    struct PtSlab* slab = nullptr;   // non-null: d points into a batch's shared block (new_cts)
 };
 // One device block shared by the plaintexts of a batch (new_pts): a block per plaintext cost a hipMalloc per
 // diagonal and, once a chain walking down the levels pushed the cache over its cap, thousands of hipFree's
@@ -646,6 +647,29 @@ static fhs_status new_pts(fhs_context* c, size_t count, int ci, double scale, fh
                 8 * count * per, slab->bytes);
     for (size_t k = 0; k < count; ++k) {
         outs[k] = new fhs_plaintext{c, slab->base + k * per, ci, l, scale, slab};
+        ++slab->refs;
+        ctx_retain(c);
+    }
+    return FHS_OK;
+}
+// `count` new ciphertexts in one device block, ciphertext k at base + k ncomp l N words (a batch result that one
+// launch writes as count x ncomp contiguous components).  The block returns to the cache when the last of them
+// is destroyed.  On failure nothing is left allocated.
+static fhs_status new_cts(fhs_context* c, int count, int ncomp, int ci, double scale, std::vector<fhs_ciphertext*>& outs) {
+    const int l = c->L0 + 1 - ci;
+    if (l < 1) return fail(FHS_ERR_LEVEL, "chain index out of range");
+    outs.assign(count, nullptr);
+    if (count == 1) return new_ct(c, ncomp, ci, scale, &outs[0]);
+    const size_t per = (size_t)ncomp * l * c->N;
+    auto* slab = new PtSlab{nullptr, 8 * (size_t)count * per, 0};
+    hipError_t e = dalloc(c, &slab->base, slab->bytes);
+    if (e != hipSuccess) {
+        delete slab;
+        return hip_fail(e, "ciphertext allocation");
+    }
+    for (int k = 0; k < count; ++k) {
+        outs[k] = new fhs_ciphertext{c, slab->base + (size_t)k * per, ncomp, ci, l, scale};
+        outs[k]->slab = slab;
         ++slab->refs;
         ctx_retain(c);
     }
@@ -1722,7 +1746,14 @@ extern "C" fhs_status fhs_ciphertext_destroy(fhs_ciphertext* ct) {
     {
         Guard g(c);
         if (pending_uses(c, ct)) flush(c);
-        dfree(c, ct->d, ct_bytes(ct));
+        if (ct->slab) {
+            if (--ct->slab->refs == 0) {
+                dfree(c, ct->slab->base, ct->slab->bytes);
+                delete ct->slab;
+            }
+        } else {
+            dfree(c, ct->d, ct_bytes(ct));
+        }
     }
     delete ct;
     ctx_release(c);
@@ -3266,6 +3297,129 @@ extern "C" fhs_status fhs_bsgs_inner_products_device(fhs_context* c, const fhs_c
     ENTER(c);
     if (!pts || !dst || !baby || !baby[0]) return fail(FHS_ERR_INVALID, "null argument");
     return inner_products_core(c, baby, G, pts, B, dst);
+}
+
+// ============================================================================ fused ct x ct dot products
+// Encrypted similarity scores of one query against C database chunks (ct_ct_search.py:92-106): the C sums of J
+// tensor products in one launch (k_dot_tensor) into a scratch [C][3][l][N], then ONE relinearization per chunk
+// -- a batched key switch of up to kDotKsBatch items (a = comp 2, add0 = comp 0, add1 = comp 1, as
+// fhs_relinearize) -- and one rescale launch over all 2 C components: the outputs share one device block
+// (new_cts), [C][2][l-1][N], which is exactly the layout launch_rescale writes for 2 C components.
+// Key-switch workspace bound: a batch of R items takes keyswitch_workspace_bytes(R, R, l) =
+// 8 N R (l + dn E + 2 E + 2 P) bytes (+ 16 R l N in the SEAL convention), E = l + P, dn = ceil(l / P); with
+// R <= kDotKsBatch = 64 that is 105 MB at the retrieval shape (N = 8192, l = 3, P = 1) however many chunks the
+// database has, and batches run back to back on the stream through the same workspace.
+constexpr int kDotKsBatch = 64;
+constexpr int kDotMaxChunks = 65535 / 3;
+static_assert(kDotKsBatch <= fhs_context::kMaxItems, "a key-switch batch must fit the item buffer");
+extern "C" fhs_status fhs_dot_product_many(fhs_context* c, const fhs_ciphertext* const* q, int J,
+                                           const fhs_ciphertext* const* db, int C, const fhs_relin_key* rk, int rescale,
+                                           fhs_ciphertext** outs) {
+    ENTER(c);
+    if (!q || !db || !outs) return fail(FHS_ERR_INVALID, "null argument");
+    if (J < 1 || C < 1) return fail(FHS_ERR_INVALID, "dot_product_many: J >= 1 and C >= 1");
+    // J + C J device pointers in the pointer buffer; 3 C components in one rescale launch (grid.y <= 65535)
+    if ((size_t)J * ((size_t)C + 1) > (size_t)fhs_context::kMaxPtrs || C > kDotMaxChunks)
+        return fail(FHS_ERR_INVALID, "dot_product_many: too many ciphertexts");
+    if (c->N % 128) return fail(FHS_ERR_INVALID, "dot_product_many: poly_modulus_degree must be a multiple of 128");
+    const size_t nq = (size_t)J, nd = (size_t)J * C;
+    std::vector<const uint64_t*> ptrs(nq + nd);
+    for (size_t k = 0; k < nq + nd; ++k) {
+        const fhs_ciphertext* a = k < nq ? q[k] : db[k - nq];
+        if (!a) return fail(FHS_ERR_INVALID, "null argument");
+        LIVE(a);
+        fhs_status s = same_level(q[0], a);
+        if (s != FHS_OK) return s;
+        if (a->ncomp != 2) return fail(FHS_ERR_INVALID, "multiply expects 2-component ciphertexts");
+        if (!scales_close(a->scale, k < nq ? q[0]->scale : db[0]->scale)) return fail(FHS_ERR_SCALE, "scale mismatch");
+        ptrs[k] = a->d;
+    }
+    const int ci = q[0]->ci, l = q[0]->l;
+    if (rescale && l < 2) return fail(FHS_ERR_LEVEL, "rescale_to_next: no level left (end of modulus switching chain)");
+    const size_t S = (size_t)l * c->N;
+    const double sc = q[0]->scale * db[0]->scale;
+    // every allocation before the first launch: a failure leaves nothing behind and `outs` untouched
+    uint64_t *t3 = nullptr, *relin = nullptr, *ws = nullptr, *scr = nullptr;
+    HIPCHK(scratch(c, fhs_context::SCR_BSGS_INNER, 8ull * C * 3 * S, &t3), "dot_product_many");
+    if (rk && rescale) HIPCHK(scratch(c, fhs_context::SCR_BSGS_SUM, 8ull * C * 2 * S, &relin), "dot_product_many");
+    const int Rmax = std::min(C, kDotKsBatch);
+    const size_t wsb = rk ? fhs::keyswitch_workspace_bytes(c->T, Rmax, Rmax, l) : 0;
+    if (rk) HIPCHK(scratch(c, fhs_context::SCR_KS, wsb, &ws), "key-switch workspace");
+    const int ocomp = rk ? 2 : 3;
+    if (rescale) HIPCHK(scratch(c, fhs_context::SCR_RESCALE, 8ull * ocomp * C * c->N, &scr), "rescale");
+    std::vector<fhs_ciphertext*> made;
+    fhs_status s = new_cts(c, C, ocomp, rescale ? ci + 1 : ci, rescale ? sc / (double)c->q[l - 1] : sc, made);
+    if (s != FHS_OK) return s;
+    auto bail = [&](hipError_t e, const char* where) {
+        for (fhs_ciphertext* m : made) fhs_ciphertext_destroy(m);
+        return hip_fail(e, where);
+    };
+    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    hipError_t e = stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * (nq + nd));
+    if (e != hipSuccess) return bail(e, "dot_product_many");
+    const uint64_t* const* dq = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
+    // the tensor sums land where the last stage reads them: the outputs' block itself when nothing follows
+    uint64_t* tdst = (!rk && !rescale) ? made[0]->d : t3;
+    e = fhs::launch_dot_tensor(c->T, dq, dq + J, J, C, l, tdst, c->st, tm);
+    if (e != hipSuccess) return bail(e, "dot_product_many");
+    if (rk) {
+        uint64_t* kdst = rescale ? relin : made[0]->d;   // [C][2][l][N]
+        const uint64_t* akey = key_akey(c, rk->key);
+        for (int c0 = 0; c0 < C; c0 += kDotKsBatch) {
+            const int R = std::min(kDotKsBatch, C - c0);
+            std::vector<KsItem> items(R);
+            std::vector<const uint64_t*> uniq(R);
+            for (int r = 0; r < R; ++r) {
+                const uint64_t* t = t3 + (size_t)(c0 + r) * 3 * S;
+                uint64_t* o = kdst + (size_t)(c0 + r) * 2 * S;
+                items[r] = KsItem{t + 2 * S, t, t + S, rk->key, o, o + S, 1, (uint64_t)r, akey};
+                uniq[r] = t + 2 * S;
+            }
+            e = fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), R, l,
+                                      ws, wsb, c->items_dev, c->stager, c->st, tm);
+            if (e != hipSuccess) return bail(e, "key-switch");
+        }
+    }
+    if (rescale) {
+        e = fhs::launch_rescale(c->T, rk ? relin : t3, made[0]->d, scr, ocomp * C, l, c->st, tm);
+        if (e != hipSuccess) return bail(e, "rescale");
+    }
+    for (int k = 0; k < C; ++k) outs[k] = made[k];
+    return FHS_OK;
+}
+
+// Test hook: k_dot_tensor's per-coefficient schedule (dot3_term / dot3_finish, fhs_modarith.h: accumulate, fold,
+// reduce, windows of kDotWindowMax terms adding their reduced sums) on the host for one coefficient of prime q:
+// out3 = (sum a0 b0, sum a0 b1 + a1 b0, sum a1 b1) mod q over J terms, with the fold the kernel would take for
+// this prime alone (16 products per Acc3 below 2^59, else 8).  Operands must be < q < 2^60.
+template <int FOLD>
+static void dot_accumulate_host(const RedU& R, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
+                                const uint64_t* b1, int J, uint64_t* out3) {
+    for (int j0 = 0; j0 < J; j0 += kDotWindowMax) {
+        const int Jw = std::min(kDotWindowMax, J - j0);
+        Dot3 s;
+        dot3_clear(s);
+        for (int j = 0; j < Jw; ++j)
+            dot3_term<FOLD>(s, j, unpack30(pack30(a0[j0 + j])), unpack30(pack30(a1[j0 + j])), split30(b0[j0 + j]),
+                            split30(b1[j0 + j]));
+        uint64_t prev[3] = {out3[0], out3[1], out3[2]};
+        dot3_finish(s, R, j0 ? prev : nullptr, out3);
+    }
+}
+extern "C" fhs_status fhs_debug_dot_accumulate(uint64_t q, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
+                                               const uint64_t* b1, int J, uint64_t* out3) {
+    if (!a0 || !a1 || !b0 || !b1 || !out3 || J < 1) return fail(FHS_ERR_INVALID, "debug_dot_accumulate: bad argument");
+    if (q < 3 || q >= (1ull << 60)) return fail(FHS_ERR_INVALID, "debug_dot_accumulate: q must be < 2^60");
+    for (int j = 0; j < J; ++j)
+        if (a0[j] >= q || a1[j] >= q || b0[j] >= q || b1[j] >= q)
+            return fail(FHS_ERR_INVALID, "debug_dot_accumulate: operands must be < q");
+    const uint64_t w = pm_word(q, 14);
+    const hu128 r = ~(hu128)0 / q;   // floor((2^128 - 1) / q) = floor(2^128 / q): q is odd
+    const RedU R{q, (uint64_t)r, (uint64_t)(r >> 64), (unsigned)(w & 127), (unsigned)((w >> 8) & 0xFFFFFFFFu), false, false};
+    out3[0] = out3[1] = out3[2] = 0;
+    if (q < (1ull << 59)) dot_accumulate_host<16>(R, a0, a1, b0, b1, J, out3);
+    else dot_accumulate_host<8>(R, a0, a1, b0, b1, J, out3);
+    return FHS_OK;
 }
 
 // The giant-step half of the fused BSGS alone: out = sum_j rot_{elts[j]}(inners[j]), every rotation's

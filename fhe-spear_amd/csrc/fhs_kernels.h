@@ -102,7 +102,7 @@ hipError_t launch_seal_corr(const DevTables& T, const u64* key, const u64* akey,
 
 // Optional per-kernel event timer (bench.py): rec(ctx, id, begin, stream) is called around launches.
 enum KernelId { KID_BSGS_INNER = 0, KID_MODUP = 1, KID_KS_IP = 2, KID_MODDOWN = 3, KID_KS_INTT = 4, KID_SPECIAL_INTT = 5,
-                KID_GIANT_SUM = 6, KID_GIANT_FINAL = 7, KID_RESCALE = 8, KID_COUNT = 10 };
+                KID_GIANT_SUM = 6, KID_GIANT_FINAL = 7, KID_RESCALE = 8, KID_DOT_TENSOR = 9, KID_COUNT = 10 };
 struct KTimer {
     void* ctx;
     void (*rec)(void* ctx, int id, int begin, hipStream_t st);
@@ -149,6 +149,10 @@ hipError_t launch_bsgs(const DevTables& T, const u64* const* baby_dev, const u64
 // word e: the periodic plaintexts' shadow, fhs_host.hip encode_rows_dev), 59-bit chains only.
 hipError_t launch_bsgs_inner(const DevTables& T, const u64* const* baby_dev, const u64* const* pts_dev, int G, int g0,
                              int g1, int D, int l, u64* inner, hipStream_t st, int ptl = 0);
+// out3[c] = sum_{j < J} q[j] (x) db[c J + j] for c < C (k_dot_tensor): q_dev J and db_dev C J device pointers to
+// 2-component ciphertexts at l limbs, out3 laid out [c][3][l][N].  Timed as KID_DOT_TENSOR.
+hipError_t launch_dot_tensor(const DevTables& T, const u64* const* q_dev, const u64* const* db_dev, int J, int C, int l,
+                             u64* out3, hipStream_t st, const KTimer* tm = nullptr);
 // CKKS encode on the GPU: `count` vectors of n values (real, or interleaved re/im), stride doubles
 // apart in device memory, to plaintexts outs[0..count) at l limbs, NTT form.
 // tlog (device, count bytes, or null): each row's periodicity from launch_enc_period -- rows with tlog > 0 are

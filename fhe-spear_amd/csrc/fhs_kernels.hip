@@ -2308,6 +2308,146 @@ hipError_t launch_bsgs_inner(const DevTables& T, const u64* const* baby_dev, con
     return launch_inner_t<FHS_INNER_VEC, FHS_INNER_WAVES>(T, baby_dev, pts_dev, G, g0, g1, D, l, inner, st, ptl);
 }
 
+// ============================================================================ ct x ct dot products
+// out[c] = sum_{j < J} q[j] (x) db[c J + j]  (3 components: q0 d0, q0 d1 + q1 d0, q1 d1), c < C: the
+// encrypted similarity scores of one query against C database chunks before their one relinearization
+// (ct_ct_search.py:92-106).  The ct x ct sibling of k_bsgs_inner, the same structure: a workgroup owns a
+// W = 64 VEC coefficient slice of limb i; the slice of the window's Jw query ciphertexts (both components) is
+// staged once in LDS, split-30 packed, [Jw][2][W]; each wave then streams the database ciphertexts of its
+// chunks (c = wave, wave + WAVES, ...) with non-temporal buffer loads, two components per term, a batch of
+// kDotBatch terms (2 kDotBatch loads of 16 bytes per lane) in flight.  The per-coefficient schedule --
+// accumulate, fold, reduce and its bounds -- is dot3_term / dot3_finish (fhs_modarith.h).
+// ACC: this launch covers terms [j0, j0 + Jw) of a longer dot product (`q` and `db` arrive offset by j0, db
+// keeps its row stride J) and adds to the reduced sums the earlier windows left in `out`.
+#define FHS_DOT_WAVES 8
+#define FHS_DOT_VEC 2
+constexpr int kDotBatch = 4;
+template <int VEC, int WAVES, int FOLD, bool ACC>
+__global__ void __launch_bounds__(64 * WAVES) k_dot_tensor(DevTables T, const u64* const* __restrict__ q,
+                                                          const u64* const* __restrict__ db, int J, int Jw, int C, int l,
+                                                          u64* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) u64 sb[];   // [Jw][2][W], split-30 packed
+    constexpr int W = 64 * VEC;
+    const int N = T.N;
+    const int i = blockIdx.y, n0 = blockIdx.x * W, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // uniform: the database pointers come by scalar loads
+    const size_t S = (size_t)l * N;
+    const size_t limb = (size_t)i * N;
+    const int dvoff = lane * VEC * 8, dsoff = n0 * 8;
+    u64 p[kDotBatch][2][VEC];
+    auto load_term = [&](const u64* ct, u64 (*dst)[VEC]) {
+        ld_diag<VEC>(ct + limb, dvoff, dsoff, dst[0]);
+        ld_diag<VEC>(ct + S + limb, dvoff, dsoff, dst[1]);
+    };
+    const int nb = Jw / kDotBatch;
+    // the wave's first batch is requested before the query slice is staged: the staging and its barrier
+    // overlap the stream
+    if (wave < C && nb > 0) {
+        const u64* const* d0 = db + (size_t)wave * J;
+#pragma unroll
+        for (int u = 0; u < kDotBatch; ++u) load_term(d0[u], p[u]);
+    }
+    for (int idx = tid; idx < Jw * 2 * W; idx += 64 * WAVES) {
+        const int j = idx / (2 * W), comp = (idx / W) & 1, c = idx % W;
+        sb[idx] = pack30(q[j][comp * S + limb + n0 + c]);
+    }
+    __syncthreads();
+    const RedU R = redu(PK(T, i));
+    for (int c = wave; c < C; c += WAVES) {
+        Dot3 s[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) dot3_clear(s[v]);
+        const u64* const* dc = db + (size_t)c * J;
+        int j = 0;
+        for (int bi = 0; bi < nb; ++bi, j += kDotBatch) {
+            const u64* const* nxt = bi + 1 < nb ? dc + j + kDotBatch : nullptr;
+#pragma unroll
+            for (int u = 0; u < kDotBatch; ++u) {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v)
+                    dot3_term<FOLD>(s[v], j + u, unpack30(sb[((j + u) * 2 + 0) * W + lane * VEC + v]),
+                                    unpack30(sb[((j + u) * 2 + 1) * W + lane * VEC + v]), split30(p[u][0][v]),
+                                    split30(p[u][1][v]));
+                if (nxt) load_term(nxt[u], p[u]);   // slot u's refill: the chunk's next batch
+            }
+        }
+        for (; j < Jw; ++j) {   // < kDotBatch left
+            u64 t[2][VEC];
+            load_term(dc[j], t);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v)
+                dot3_term<FOLD>(s[v], j, unpack30(sb[(j * 2 + 0) * W + lane * VEC + v]),
+                                unpack30(sb[(j * 2 + 1) * W + lane * VEC + v]), split30(t[0][v]), split30(t[1][v]));
+        }
+        u64* o = out + (size_t)c * 3 * S + limb + n0 + lane * VEC;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            u64 prev[3], r[3];
+            if constexpr (ACC) {
+                prev[0] = o[v];
+                prev[1] = o[S + v];
+                prev[2] = o[2 * S + v];
+            }
+            dot3_finish(s[v], R, ACC ? prev : nullptr, r);
+            o[v] = r[0];
+            o[S + v] = r[1];
+            o[2 * S + v] = r[2];
+        }
+        if (c + WAVES < C && nb > 0) {   // the wave's next chunk: its first batch
+            const u64* const* dn = db + (size_t)(c + WAVES) * J;
+#pragma unroll
+            for (int u = 0; u < kDotBatch; ++u) load_term(dn[u], p[u]);
+        }
+    }
+}
+template <int VEC, int WAVES>
+static hipError_t launch_dot_t(const DevTables& T, const u64* const* q, const u64* const* db, int J, int C, int l, u64* out,
+                               hipStream_t st) {
+    constexpr int W = 64 * VEC;
+    static bool attr = false;
+    if (!attr) {   // dynamic LDS above 64 KiB must be opted into
+        for (const void* k : {reinterpret_cast<const void*>(&k_dot_tensor<VEC, WAVES, 8, false>),
+                              reinterpret_cast<const void*>(&k_dot_tensor<VEC, WAVES, 8, true>),
+                              reinterpret_cast<const void*>(&k_dot_tensor<VEC, WAVES, 16, false>),
+                              reinterpret_cast<const void*>(&k_dot_tensor<VEC, WAVES, 16, true>)}) {
+            hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)(kDotWindowMax * 2 * W * 8));
+            if (e != hipSuccess) return e;
+        }
+        attr = true;
+    }
+    // J <= 64: one launch over every term; else windows of 64, each adding to the previous ones' reduced sums
+    for (int j0 = 0; j0 < J; j0 += kDotWindowMax) {
+        const int Jw = std::min(kDotWindowMax, J - j0);
+        const size_t lds = (size_t)Jw * 2 * W * 8;
+        const dim3 grid(T.N / W, l), block(64 * WAVES);
+        if (T.max_qbits <= 59) {
+            if (j0)
+                hipLaunchKernelGGL((k_dot_tensor<VEC, WAVES, 16, true>), grid, block, lds, st, T, q + j0, db + j0, J, Jw, C, l,
+                                   out);
+            else
+                hipLaunchKernelGGL((k_dot_tensor<VEC, WAVES, 16, false>), grid, block, lds, st, T, q, db, J, Jw, C, l, out);
+        } else {
+            if (j0)
+                hipLaunchKernelGGL((k_dot_tensor<VEC, WAVES, 8, true>), grid, block, lds, st, T, q + j0, db + j0, J, Jw, C, l,
+                                   out);
+            else
+                hipLaunchKernelGGL((k_dot_tensor<VEC, WAVES, 8, false>), grid, block, lds, st, T, q, db, J, Jw, C, l, out);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+hipError_t launch_dot_tensor(const DevTables& T, const u64* const* q_dev, const u64* const* db_dev, int J, int C, int l,
+                             u64* out3, hipStream_t st, const KTimer* tm) {
+    if (T.N % (64 * FHS_DOT_VEC) || J < 1 || C < 1) return hipErrorInvalidValue;
+    FHS_TMARK(tm, KID_DOT_TENSOR, 1, st);
+    const hipError_t e = launch_dot_t<FHS_DOT_VEC, FHS_DOT_WAVES>(T, q_dev, db_dev, J, C, l, out3, st);
+    FHS_TMARK(tm, KID_DOT_TENSOR, 0, st);
+    return e;
+}
+
 // Hadamard (every giant group's inner product; skipped when pts_dev is null and `inner` already holds
 // them), then the giant steps: INTT + centred ModUp + NTT of
 // the B - 1 inner products (one ModUp each), key inner products with the automorphism applied on the

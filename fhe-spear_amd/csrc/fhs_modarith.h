@@ -99,12 +99,20 @@ __device__ __forceinline__ u64 shoup(u64 a, u64 w, u64 wp, u64 q) { return csub(
 
 // Barrett reduction of a 128-bit value with r = floor(2^128 / q) = (r1:r0).  The quotient
 // estimate is short by at most 2, so two corrections give the canonical residue in [0, q).
-__device__ __forceinline__ u64 barrett128(u64 lo, u64 hi, u64 q, u64 r0, u64 r1) {
-    u64 c = __umul64hi(lo, r0);
-    u64 a_lo = lo * r1, a_hi = __umul64hi(lo, r1);
+// (__host__ too: the host test hooks run the kernels' own reduction, fhs_debug_dot_accumulate)
+__host__ __device__ __forceinline__ u64 umulhi64_hd(u64 a, u64 b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(a, b);
+#else
+    return (u64)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+__host__ __device__ __forceinline__ u64 barrett128(u64 lo, u64 hi, u64 q, u64 r0, u64 r1) {
+    u64 c = umulhi64_hd(lo, r0);
+    u64 a_lo = lo * r1, a_hi = umulhi64_hd(lo, r1);
     u64 t1 = a_lo + c;
     u64 t3 = a_hi + (t1 < c);
-    u64 b_lo = hi * r0, b_hi = __umul64hi(hi, r0);
+    u64 b_lo = hi * r0, b_hi = umulhi64_hd(hi, r0);
     u64 s = t1 + b_lo;
     u64 carry = b_hi + (s < t1);
     u64 qest = hi * r1 + t3 + carry;
@@ -144,7 +152,7 @@ __host__ __device__ __forceinline__ u64 pm_reduce128(u64 lo, u64 hi, u64 q, unsi
     const u64 h3 = (t_hi << sb) | (t_lo >> b);
     return csub((u64)(uint32_t)h3 * d + (t_lo & mask), q);
 }
-__device__ __forceinline__ u64 addmod(u64 a, u64 b, u64 q) { return csub(a + b, q); }
+__host__ __device__ __forceinline__ u64 addmod(u64 a, u64 b, u64 q) { return csub(a + b, q); }
 __device__ __forceinline__ u64 submod(u64 a, u64 b, u64 q) { return a >= b ? a - b : a + q - b; }
 
 // Split-30 lazy accumulation of sums of 64x64 products for residues < 2^60 (every context prime
@@ -158,14 +166,14 @@ struct Acc3 {
 struct Split30 {
     uint32_t lo, hi;
 };
-__device__ __forceinline__ Split30 split30(u64 x) { return Split30{(uint32_t)x & 0x3FFFFFFFu, (uint32_t)(x >> 30)}; }
+__host__ __device__ __forceinline__ Split30 split30(u64 x) { return Split30{(uint32_t)x & 0x3FFFFFFFu, (uint32_t)(x >> 30)}; }
 __host__ __device__ __forceinline__ u64 pack30(u64 x) { return (u64)(((uint32_t)x) & 0x3FFFFFFFu) | ((x >> 30) << 32); }
 __host__ __device__ __forceinline__ Split30 unpack30(u64 p) { return Split30{(uint32_t)p, (uint32_t)(p >> 32)}; }
 // The compiler forms M's two partials separately and adds their sum (a v_lshl_add_u64 more per product);
 // forcing the chain -- one v_mad_u64_u32 per partial as inline asm, or an empty asm between M's two mads --
 // measured slower on MI355X (r04c: key inner products 1.62 -> 1.90 ms/step, Hadamard 1.93 -> 1.96-1.98;
 // the asm blocks unrolling and adds hazard nops), so the plain expression stays.
-__device__ __forceinline__ void acc3_mac(Acc3& a, Split30 x, Split30 y) {
+__host__ __device__ __forceinline__ void acc3_mac(Acc3& a, Split30 x, Split30 y) {
     a.L += mul32w(x.lo, y.lo);
     a.M += mul32w(x.lo, y.hi);
     a.M += mul32w(x.hi, y.lo);
@@ -262,7 +270,7 @@ __host__ __device__ __forceinline__ u64 convert3x_b59(u64 V0, u64 p1, u64 p2, ui
 }
 
 // c += L + M 2^30 + H 2^60 (< 2^123 for 8 products), then clear
-__device__ __forceinline__ void acc3_fold(u128& c, Acc3& a) {
+__host__ __device__ __forceinline__ void acc3_fold(u128& c, Acc3& a) {
     u64 lo = a.L, hi = 0;
     u64 t = a.M << 30;
     lo += t;
@@ -375,9 +383,60 @@ __device__ __forceinline__ RedU redu(const PrimeK& P) {
     return RedU{rfl64(P.q), rfl64(P.r0), rfl64(P.r1), (unsigned)(pm & 127), (unsigned)((pm >> 8) & 0xFFFFFFFFu),
                 (pm & 128) != 0, ((pm >> 40) & 1) != 0};
 }
-__device__ __forceinline__ u64 reduce128(u64 lo, u64 hi, const RedU& R) {
+__host__ __device__ __forceinline__ u64 reduce128(u64 lo, u64 hi, const RedU& R) {
     if (R.b) return pm_reduce128(lo, hi, R.q, R.b, R.d);
     return barrett128(lo, hi, R.q, R.r0, R.r1);
+}
+
+// ---- ct x ct dot product at one coefficient (k_dot_tensor in fhs_kernels.hip; the host test hook
+// fhs_debug_dot_accumulate runs the same routines).  Term j multiplies the query's (q0, q1) by the database
+// ciphertext's (d0, d1) into the three tensor sums
+//   s0 += q0 d0,   s1 += q0 d1 + q1 d0,   s2 += q1 d1.
+// Bounds.  Residues are < 2^60, so the split-30 halves are < 2^30 and each partial product is <= (2^30 - 1)^2
+// < 2^60.  Per product Acc3's L and H take one partial and M two: after k products L, H < k 2^60 and
+// M < k 2^61, so k = 8 products keep all three below 2^64 (FOLD = 8, any prime).  When every prime is < 2^59
+// (T.max_qbits <= 59) the high halves are < 2^29: a product adds < 2^60 to L, < 2 * 2^59 = 2^60 to M and
+// < 2^58 to H, so k = 16 products fit (FOLD = 16).  s0 and s2 take one product per term and fold every
+// FOLD terms; s1 takes two and folds every FOLD / 2 terms, i.e. after the same FOLD products.
+// Each product is < 2^120, and a window holds at most kDotWindowMax = 64 terms: the 128-bit sums reach at
+// most 64 2^120 = 2^126 (s0, s2) and 128 2^120 = 2^127 (s1) < 2^128.  Longer dot products add the reduced
+// sums of further windows (dot3_finish).
+constexpr int kDotWindowMax = 64;
+struct Dot3 {
+    Acc3 a0, a1, a2;
+    u128 c0, c1, c2;
+};
+__host__ __device__ __forceinline__ void dot3_clear(Dot3& s) {
+    s.a0 = s.a1 = s.a2 = Acc3{0, 0, 0};
+    s.c0 = s.c1 = s.c2 = u128{0, 0};
+}
+// term j (0-based inside the window) and the folds due after it
+template <int FOLD>
+__host__ __device__ __forceinline__ void dot3_term(Dot3& s, int j, Split30 q0, Split30 q1, Split30 d0, Split30 d1) {
+    static_assert(FOLD == 8 || FOLD == 16, "Acc3 takes 8 products (any prime) or 16 (primes < 2^59)");
+    acc3_mac(s.a0, q0, d0);
+    acc3_mac(s.a1, q0, d1);
+    acc3_mac(s.a1, q1, d0);
+    acc3_mac(s.a2, q1, d1);
+    if (((j + 1) & (FOLD / 2 - 1)) == 0) acc3_fold(s.c1, s.a1);
+    if (((j + 1) & (FOLD - 1)) == 0) {
+        acc3_fold(s.c0, s.a0);
+        acc3_fold(s.c2, s.a2);
+    }
+}
+// the window's three sums mod q; prev (non-null: the reduced sums of the windows before) is added
+__host__ __device__ __forceinline__ void dot3_finish(Dot3& s, const RedU& R, const u64* prev, u64 out[3]) {
+    acc3_fold(s.c0, s.a0);
+    acc3_fold(s.c1, s.a1);
+    acc3_fold(s.c2, s.a2);
+    out[0] = reduce128(s.c0.lo, s.c0.hi, R);
+    out[1] = reduce128(s.c1.lo, s.c1.hi, R);
+    out[2] = reduce128(s.c2.lo, s.c2.hi, R);
+    if (prev) {
+        out[0] = addmod(out[0], prev[0], R.q);
+        out[1] = addmod(out[1], prev[1], R.q);
+        out[2] = addmod(out[2], prev[2], R.q);
+    }
 }
 // Any 64-bit value of a pseudo-Mersenne prime (b >= 41) to [0, q): one fold, one subtraction.
 __device__ __forceinline__ u64 pm_fold64(u64 x, const RedU& R) {

@@ -157,6 +157,8 @@ _SIGS = {
     "fhs_bsgs_from_cpu": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _u64p, C.c_int, C.c_int, C.c_int, C.c_double, _vp,
                                     C.POINTER(_vp)]),
     "fhs_bsgs_inner_products": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.POINTER(_vp)]),
+    "fhs_dot_product_many": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _vp, C.c_int,
+                                       C.POINTER(_vp)]),
     "fhs_bsgs_giant_steps": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _u64p, _vp, C.POINTER(_vp)]),
     "fhs_bsgs_inner_products_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _vp]),
     "fhs_bsgs_giant_steps_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, _u64p, _vp, C.POINTER(_vp)]),
@@ -897,6 +899,41 @@ def bsgs_giant_steps(ctx, inners, elts, gk):
     return _ct(ctx, _lib.fhs_bsgs_giant_steps, hh, k, ep, gk._h, what="bsgs_giant_steps")
 
 
+# ------------------------------------------------------------------ encrypted retrieval scores
+def _chunk_rows(what, query, chunks):
+    J = len(query)
+    if J < 1 or len(chunks) < 1:
+        raise ValueError(f"{what}: needs at least one query ciphertext and one chunk")
+    for c, row in enumerate(chunks):
+        if len(row) != J:
+            raise ValueError(f"{what}: chunk {c} has {len(row)} entries for a query of {J} (ragged input)")
+    return J, len(chunks)
+
+
+def dot_product_many(ctx, query, chunks, rk=None, rescale=True):
+    """Extension: encrypted dot-product scores of one query against C database chunks (the reference's
+    similarity join, ct_ct_search.py:92-106) -- [rescale](relinearize(sum_j multiply(query[j], chunks[c][j])))
+    for every chunk c, limb-identical to that composition with ONE relinearization and ONE rescale per chunk
+    (fhs_dot_product_many).  chunks: C sequences of J = len(query) ciphertexts.  rk=None keeps the 3-component
+    sums; rescale=False keeps the product scale and the level.  The C results share one device block."""
+    J, Cn = _chunk_rows("dot_product_many", query, chunks)
+    qq = (_vp * J)(*[c._h for c in query])
+    dd = (_vp * (J * Cn))(*[c._h for row in chunks for c in row])
+    hs = (_vp * Cn)()
+    _check(_lib.fhs_dot_product_many(ctx._h, qq, J, dd, Cn, None if rk is None else rk._h, 1 if rescale else 0, hs),
+           "dot_product_many")
+    return [ciphertext(ctx, _vp(hs[c])) for c in range(Cn)]
+
+
+def dot_product_plain_many(ctx, query, pt_chunks, rescale=True):
+    """Extension: the CT-PT scores of fhe_common.batched_dot_products (fc:112-147) --
+    [rescale](sum_j multiply_plain(query[j], pt_chunks[c][j])) for every chunk c, through the BSGS Hadamard
+    (bsgs_inner_products with the query as the baby steps and one "giant group" per chunk)."""
+    J, Cn = _chunk_rows("dot_product_plain_many", query, pt_chunks)
+    sums = bsgs_inner_products(ctx, list(query), [p for row in pt_chunks for p in row], J, Cn)
+    return [rescale_to_next(ctx, s) for s in sums] if rescale else sums
+
+
 # ------------------------------------------------------------------ bootstrapping primitives
 def linear_transform(ctx, ct_baby, pts, G, giant_elts, gk, rescale=True):
     """Generalised fused BSGS (CoeffToSlot / SlotToCoeff groups of ckks_bootstrapper):
@@ -1099,7 +1136,7 @@ class Event:
 
 
 KERNEL_IDS = {"k_bsgs_inner": 0, "k_modup": 1, "k_ks_ip": 2, "k_moddown": 3, "k_ks_intt": 4,
-              "k_ks_special_intt": 5, "k_giant_sum": 6, "k_giant_final": 7, "rescale": 8}
+              "k_ks_special_intt": 5, "k_giant_sum": 6, "k_giant_final": 7, "rescale": 8, "k_dot_tensor": 9}
 
 
 def kernel_timer_arm(ctx, names=None):

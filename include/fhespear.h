@@ -250,6 +250,19 @@ fhs_status fhs_bsgs_inner_products_device(fhs_context* ctx, const fhs_ciphertext
                                           const fhs_plaintext* const* pts, int B, uint64_t* dst);
 fhs_status fhs_bsgs_giant_steps_device(fhs_context* ctx, const uint64_t* src, int k, int chain_index, double scale,
                                        const uint64_t* elts, const fhs_galois_keys* gk, fhs_ciphertext** out);
+/* Extension (ct_ct_search.py:92-106, fc:169-194): encrypted dot-product scores of one query against C chunks.
+ *   outs[c] = [rescale]( [relinearize]( sum_{j<J} q[j] (x) db[c*J + j] ) ),  c < C
+ * limb-identical to  t = multiply(q[0], db[cJ]); t = add(t, multiply(q[j], db[cJ+j])) ...;
+ * relinearize(t, rk); rescale_to_next.  rk = NULL: 3-component result.  rescale = 0: product scale kept.
+ * Every input has 2 components; all inputs share one chain index (else FHS_ERR_LEVEL), all q one scale and all db
+ * one scale (else FHS_ERR_SCALE); J >= 1, 1 <= C <= 21845, J (C + 1) <= 65536; rescale at the last level is
+ * FHS_ERR_LEVEL.
+ * The relinearization follows the context's key-switch mode.  On failure nothing is left allocated and outs is
+ * untouched.  Lifetime: the C results share one device block (as the plaintexts of a batch creator do), returned
+ * to the cache when the LAST of them is destroyed. */
+fhs_status fhs_dot_product_many(fhs_context* ctx, const fhs_ciphertext* const* q, int J,
+                                const fhs_ciphertext* const* db, int C, const fhs_relin_key* rk,
+                                int rescale, fhs_ciphertext** outs);
 /* Extension (no reference symbol): bg:198-203 + bg:361-432 on the device -- the D diagonals of the
  * D x D row-major matrix M1 (complex: M1 + i M2; M2 = NULL for real), group g = k / G rolled by g G,
  * tiled to N/2 slots, encoded at `scale` / `chain_index`.  Limb-identical to encode_*_vector_batch
@@ -298,8 +311,9 @@ fhs_status fhs_event_destroy(void* ev);
 /* Per-kernel device time from HIP events recorded on the context stream around each launch.
  * Kernel ids: 0 k_bsgs_inner (ct x pt Hadamard-accumulate), 1 k_modup (ModUp + NTT), 2 k_ks_ip
  * (key inner product), 3 k_moddown, 4 k_ks_intt, 5 k_ks_special_intt, 6 k_giant_sum,
- * 7 k_giant_final, 8 rescale.  arm(mask) enables ids (bit i); timer() reports kernel_id's
- * accumulated ms / launch count and optionally resets every accumulator. */
+ * 7 k_giant_final, 8 rescale, 9 k_dot_tensor (ct x ct dot-product tensor sums).  arm(mask) enables
+ * ids (bit i); timer() reports kernel_id's accumulated ms / launch count and optionally resets every
+ * accumulator. */
 fhs_status fhs_kernel_timer_arm(fhs_context* ctx, uint32_t mask);
 fhs_status fhs_kernel_timer(fhs_context* ctx, int kernel_id, float* ms, int* launches, int reset);
 /* device-to-device copies of ciphertext limbs to / from caller-owned HBM (RCCL gather in bench.py) */
@@ -328,6 +342,12 @@ fhs_status fhs_debug_modup_xform(const uint64_t* q3, const uint64_t* y3, uint64_
 /* Test hook: ModDown's X form (k_special_x + moddown_convert3x arithmetic, on the host): special residues y3
  * over primes p3 (< 2^59) into target prime q; *out = (sum_k y3[k] P/p3[k]) mod q. */
 fhs_status fhs_debug_moddown_xform(const uint64_t* p3, const uint64_t* y3, uint64_t q, uint64_t* out);
+/* Test hook: k_dot_tensor's per-coefficient schedule (split-30 accumulate, Acc3 folds, 128-bit sums, one reduction
+ * per sum, windows of 64 terms adding their reduced sums -- the kernel's own __host__ __device__ routines) run on
+ * the host for one coefficient of prime q < 2^60: out3 = (sum a0 b0, sum a0 b1 + a1 b0, sum a1 b1) mod q over J
+ * terms.  Operands must be < q. */
+fhs_status fhs_debug_dot_accumulate(uint64_t q, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
+                                    const uint64_t* b1, int J, uint64_t* out3);
 
 #ifdef __cplusplus
 }
