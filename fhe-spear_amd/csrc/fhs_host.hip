@@ -519,24 +519,6 @@ static void evict_cold(fhs_context* c, size_t keep) {
     ctx_sync(c);
     for (void* p : victims) (void)hipFree(p);
 }
-// FHESPEAR_CONTIG_BYTES=n (default 0 = never): allocations of at least n bytes ask for physically contiguous memory
-// (hipDeviceMallocContiguous), falling back to plain hipMalloc when refused.  Round 6 (tools/debug/alloc_spread.py,
-// profiles/r06/alloc_spread/): the Hadamard's time follows where its 9.66 GB diagonal slab lands in HBM -- the same
-// process, clocks and data re-allocated ten times ran 1.79-2.02 ms (hipMalloc) and 1.75-2.01 ms (contiguous), the
-// contiguous placements mostly at the fast end (mean -2 % and -6 % on two boxes); but on the bench's own
-// allocation sequence both landed at 2.00-2.05 ms (4 + 4 interleaved runs, profiles/r06/alloc_spread/ab_bench.txt),
-// so it stays off.
-static hipError_t dev_malloc(void** v, size_t bytes) {
-    static const size_t contig = [] {
-        const char* e = getenv("FHESPEAR_CONTIG_BYTES");
-        return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)0;
-    }();
-    if (contig && bytes >= contig) {
-        if (hipExtMallocWithFlags(v, bytes, hipDeviceMallocContiguous) == hipSuccess) return hipSuccess;
-        (void)hipGetLastError();
-    }
-    return hipMalloc(v, bytes);
-}
 static hipError_t dalloc(fhs_context* c, uint64_t** p, size_t bytes) {
     bytes = bytes ? bytes : 8;
     c->size_tick[bytes] = ++c->cache_tick;
@@ -549,12 +531,12 @@ static hipError_t dalloc(fhs_context* c, uint64_t** p, size_t bytes) {
         return hipSuccess;
     }
     void* v = nullptr;
-    hipError_t e = dev_malloc(&v, bytes);
+    hipError_t e = hipMalloc(&v, bytes);
     if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {   // give every cache back, retry once
         (void)hipGetLastError();
         trim_cache(c);
         trim_other_caches(c);
-        e = dev_malloc(&v, bytes);
+        e = hipMalloc(&v, bytes);
     }
     if (e == hipSuccess) {
         *p = (uint64_t*)v;
@@ -632,19 +614,13 @@ static fhs_status new_pts(fhs_context* c, size_t count, int ci, double scale, fh
     for (size_t k = 0; k < count; ++k) outs[k] = nullptr;
     if (count == 0) return FHS_OK;
     if (count == 1) return new_pt(c, ci, scale, outs);
-    // FHESPEAR_PT_PAD_WORDS (experiment, default 0): words of padding between a slab's plaintexts (read per call)
-    const char* padv = getenv("FHESPEAR_PT_PAD_WORDS");
-    const size_t pad = padv ? (strtoull(padv, nullptr, 10) + 1) & ~(size_t)1 : 0;
-    const size_t per = (size_t)l * c->N + pad;
+    const size_t per = (size_t)l * c->N;
     auto* slab = new PtSlab{nullptr, 8 * count * per, 0};
     hipError_t e = dalloc_fit(c, &slab->base, &slab->bytes);
     if (e != hipSuccess) {
         delete slab;
         return hip_fail(e, "plaintext allocation");
     }
-    if (getenv("FHESPEAR_TRACE_SLABS"))
-        fprintf(stderr, "[fhespear] slab %p: %zu plaintexts, %zu bytes (block %zu)\n", (void*)slab->base, count,
-                8 * count * per, slab->bytes);
     for (size_t k = 0; k < count; ++k) {
         outs[k] = new fhs_plaintext{c, slab->base + k * per, ci, l, scale, slab};
         ++slab->refs;
@@ -822,11 +798,6 @@ static hipError_t stage_h2d(void* user, void* dst, const void* src, size_t bytes
 }
 
 // ---------------------------------------------------------------- SEAL-convention hoisting
-// FHESPEAR_SEAL_HOIST=0 keeps SEAL's per-rotation decomposition for every flush (A/B and test knob)
-static bool seal_hoist_enabled() {
-    const char* v = getenv("FHESPEAR_SEAL_HOIST");
-    return !v || strcmp(v, "0") != 0;
-}
 static size_t seal_corr_bytes(const fhs_context* c, int l) { return 8ull * 2 * (l + c->P) * c->N; }
 // the corrections of `key` (null: of every key), returned to the block cache in stream order
 static void drop_seal_corr(fhs_context* c, const uint64_t* key) {
@@ -920,7 +891,7 @@ static fhs_status flush(fhs_context* c) {
     ht.mark("flush: workspace");
     if (e != hipSuccess) return drop_pending(c, hip_fail(e, "key-switch workspace"));
     fhs::SealHoist* sh = nullptr;
-    if (c->T.ks_seal && U < R && seal_hoist_enabled()) {   // SEAL convention: one ModUp per shared input
+    if (c->T.ks_seal && U < R) {   // SEAL convention: one ModUp per shared input
         e = seal_prepare(c, items, l);
         if (e == hipSuccess) sh = &c->seal_hoist;
         else if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {

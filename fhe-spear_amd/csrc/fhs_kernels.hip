@@ -4,8 +4,8 @@
 //   k_ntt_fwd / k_ntt_inv          batched per-limb negacyclic NTT (one limb per workgroup, LDS-resident)
 //   k_eltwise / k_tensor           ct add/sub/negate, ct x pt Hadamard (pb:167, 181), ct x ct tensor (pb:177)
 //   k_rescale_*                    divide-and-round by q_last (pb:185, bg:484)
-//   k_ks_intt / k_modup_ip /       hybrid key-switch: automorphism+INTT, fused ModUp+NTT+key inner product,
-//   k_ks_special_intt / k_moddown  ModDown (pb:203 rotate, pb:183 relinearize)
+//   k_ks_intt / k_modup / k_ks_ip  hybrid key-switch: INTT + centring, ModUp + NTT, key inner product with the
+//   k_ks_special_intt / k_moddown  automorphism on the fly, ModDown (pb:203 rotate, pb:183 relinearize)
 //   k_bsgs_inner                   sum_b baby[b] (.) pt[gG+b] for every giant group g (bg:465-476)
 //   k_giant_sum / k_giant_final    giant-step rotations summed exactly in the extended basis (bg:478-483)
 //   k_sample / k_swk / ...         deterministic key generation and encryption helpers
@@ -22,6 +22,7 @@ typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 #include "fhs_ntt.h"
 #include "fhs_buffer.h"
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,11 +33,6 @@ typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 // alternatives and their records are listed in DESIGN.md and profiles/r0*/ab_*).
 #define FHS_INNER_WAVES 16     // waves per k_bsgs_inner workgroup sharing one LDS baby-step slice
 #define FHS_INNER_VEC 2        // consecutive coefficients per lane in k_bsgs_inner (16-byte loads)
-#define FHS_MODDOWN_HALF 1     // k_moddown_h: half-limb LDS
-#define FHS_INTT_HALF 1        // k_ks_intt_h: half-limb LDS inverse NTT
-#ifndef FHS_MODUP_QUADPAIR
-#define FHS_MODUP_QUADPAIR 1   // k_modup_h block decode: 1 = xcd_quadpair (inputs read by 4 XCDs), 0 = xcd_tinner
-#endif
 #ifndef FHS_MODUPH_CH
 #define FHS_MODUPH_CH 2        // k_modup_h: coefficient pairs per conversion chunk
 #endif
@@ -87,14 +83,6 @@ __device__ __forceinline__ bool xcd_tinner(int E, int M, int& t, int& m) {
     m = k / nx;
     return true;
 }
-// m-major: XCD x takes the inputs m == x (mod 8), all limbs t of one m back to back
-__device__ __forceinline__ bool xcd_mmajor(int E, int M, int& t, int& m) {
-    const int b = blockIdx.x, x = b & 7, k = b >> 3, nm = (M - x + 7) >> 3;
-    if (nm <= 0 || k >= nm * E) return false;
-    m = x + 8 * (k / E);
-    t = k % E;
-    return true;
-}
 // quad-pair: XCD x takes the limbs t == x (mod 4) of the inputs m == x / 4 (mod 2) -- ~E/4 primes' twiddle
 // tables per XCD L2 (2.5 MiB at E = 39) and each input read by 4 XCDs instead of all 8 (t-inner as
 // xcd_tinner).  Grid = 8 * ceil(E/4) * ceil(M/2).
@@ -107,7 +95,6 @@ __device__ __forceinline__ bool xcd_quadpair(int E, int M, int& t, int& m) {
     m = mh + 2 * (k / nx);
     return true;
 }
-__host__ __device__ __forceinline__ int xcd_grid_m(int E, int M) { return 8 * ((M + 7) / 8) * E; }
 // plain: blockIdx.x = t + E * m (t fastest)
 __device__ __forceinline__ bool plain_tm(int E, int M, int& t, int& m) {
     t = blockIdx.x % E;
@@ -637,16 +624,12 @@ __global__ void __launch_bounds__((ntt_threads<LOGN, true>())) k_rescale_ntt_hs(
 #ifndef FHS_SPLIT_MAX_WG
 #define FHS_SPLIT_MAX_WG 256   // below this many workgroups a launch is latency-bound: one workgroup per half-limb
 #endif
-#ifndef FHS_RESCALE_SPLIT
-#define FHS_RESCALE_SPLIT 1   // 0: the one-workgroup-per-limb rescale at N = 32768 too (A/B and test knob)
-#endif
 hipError_t launch_rescale(const DevTables& T, const u64* in, u64* out, u64* scratch, int ncomp, int l,
                           hipStream_t st, const KTimer* tm) {
     FHS_TMARK(tm, KID_RESCALE, 1, st);
-    static const bool split_off = getenv("FHESPEAR_RESCALE_UNSPLIT") != nullptr;
     FHS_DISPATCH_LOGN(T.logN, {
-        if constexpr (LOGN == 15 && FHS_RESCALE_SPLIT) {
-            if (!split_off && ncomp <= 2) {
+        if constexpr (LOGN == 15) {
+            if (ncomp <= 2) {
                 hipLaunchKernelGGL((k_rescale_intt_hs<LOGN>), dim3(2, ncomp), dim3(ntt_threads<LOGN, true>()), 0, st, T,
                                    in, scratch, l);
                 hipLaunchKernelGGL((k_rescale_ntt_hs<LOGN>), dim3(l - 1, ncomp, 2), dim3(ntt_threads<LOGN, true>()), 0, st,
@@ -745,7 +728,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 32, 4) k_ks_intt_h(DevTables T, 
 template <int LOGN>
 static bool ks_intt_half(int nwg) {
     if (LOGN <= 14 && nwg < FHS_FULL_FORM_MAX_WG) return false;
-    return (FHS_INTT_HALF && LOGN >= 9) || ntt_half<LOGN>();
+    return ks_uses_half(LOGN);
 }
 
 // Exact centred-extension count, slow path (|frac - 1/2| < 2^-58; never seen on random data
@@ -954,11 +937,11 @@ __global__ void __launch_bounds__((1 << LOGN) / 16) k_modup(DevTables T, const u
 template <int LOGN, bool B59>
 __device__ __forceinline__ void modup_convert3x(const u64* yb, const u64* xt, const RedU& R, const u64* tw, int tid,
                                                 u64* lds, u64 hi[16]) {
-    constexpr int N = 1 << LOGN, NH = N / 2, TH = N / 32, CH = FHS_MODUPH_CH;
+    constexpr int N = 1 << LOGN, NH = N / 2, TH = N / 32;
     const __amdgpu_buffer_rsrc_t ry = brsrc(yb, 3 * N * 8);
     const uint32_t e1 = (uint32_t)xt[0];
     const Split30 e2 = unpack30(xt[1]);
-    const u64 c3 = xt[2], m = R.q, q2 = 2 * m;
+    const u64 c3 = xt[2], m = R.q;
     const int vo = tid * 8;
     const Tw4 w4 = ld_tw4(tw);
 #pragma unroll
@@ -1119,7 +1102,8 @@ __device__ __forceinline__ void modup_h_body(const DevTables& T, const u64* acoe
         }
 #pragma unroll
         for (int k = 0; k < CH; ++k) {   // global stage 0: (e, e + N/2), twiddle psi^rev(1)
-            const int e = tid + (ch * CH + k) * TH;
+            // unused, but kept: without it the compiler schedules this path's kernels differently
+            [[maybe_unused]] const int e = tid + (ch * CH + k) * TH;
             const u64 tt = shoup_lazy(x[CH + k], w0, w0p, m);
             lds[row_pad<TH>(tid, ch * CH + k)] = x[k] + tt;
             hi[ch * CH + k] = x[k] + (q2 - tt);
@@ -1183,30 +1167,29 @@ __global__ void __launch_bounds__((1 << LOGN) / 32, 4) k_modup_h(DevTables T, co
     __shared__ __attribute__((aligned(16))) u64 lds[modup_h_lds_words<LOGN>()];
     const int E = l + T.P, dn = (l + T.P - 1) / T.P;
     int t, mi;
-    if (!(FHS_MODUP_QUADPAIR ? xcd_quadpair(E, dn * U, t, mi) : xcd_tinner(E, dn * U, t, mi))) return;
+    if (!xcd_quadpair(E, dn * U, t, mi)) return;
     modup_h_body<LOGN, DP, B59>(T, acoef, vcnt, ext, l, t, mi, threadIdx.x, lds);
 }
 
+// The kernel and its grid are chosen first, the launch is written once (as in ks_moddown_stage)
 template <int LOGN>
 static void launch_modup(const DevTables& T, const u64* const* uniq, const u64* acoef, const unsigned char* vcnt,
                          u64* ext, int l, int U, hipStream_t st) {
-    const int E = l + T.P, dn = (l + T.P - 1) / T.P;
-    const int mgrid = xcd_grid(E, dn * U);
-    const dim3 g(FHS_MODUP_QUADPAIR ? xcd_grid_q(E, dn * U) : mgrid), b((1 << LOGN) / 32);
-    static_assert(modup_uses_half(LOGN) || !ntt_half<LOGN>(), "the full-limb ModUp needs N <= 16384");
-    if (!modup_uses_half(LOGN))   // residues + counts (launch_centered wrote no X form: modup_xform is false)
-        hipLaunchKernelGGL((k_modup<LOGN>), dim3(mgrid), dim3((1 << LOGN) / 16), 0, st, T, uniq, acoef, vcnt, ext, l, U);
-    else if (modup_xform(T, l) && T.conv_b59)   // every digit full (3 limbs), X form, 59-bit primes
-        hipLaunchKernelGGL((k_modup_h<LOGN, 3, true>), g, b, 0, st, T, uniq, acoef, vcnt, ext, l, U);
-    else if (modup_xform(T, l))   // every digit of this level full (3 limbs), X form (launch_centered)
-        hipLaunchKernelGGL((k_modup_h<LOGN, 3, false>), g, b, 0, st, T, uniq, acoef, vcnt, ext, l, U);
-    else if (T.modup_dp == 1)
-        if (T.all_b59)   // SEAL's 59-bit chains: compile-time lazy NTT and folded stores
-            hipLaunchKernelGGL((k_modup_h<LOGN, 1, true>), g, b, 0, st, T, uniq, acoef, vcnt, ext, l, U);
-        else
-            hipLaunchKernelGGL((k_modup_h<LOGN, 1, false>), g, b, 0, st, T, uniq, acoef, vcnt, ext, l, U);
-    else
-        hipLaunchKernelGGL((k_modup_h<LOGN, 0, false>), g, b, 0, st, T, uniq, acoef, vcnt, ext, l, U);
+    const int E = l + T.P, M = (l + T.P - 1) / T.P * U;
+    void (*k)(DevTables, const u64* const*, const u64*, const unsigned char*, u64*, int, int);
+    dim3 g(xcd_grid_q(E, M)), b((1 << LOGN) / 32);   // k_modup_h
+    if (!ks_uses_half(LOGN)) {   // residues + counts (launch_centered wrote no X form: modup_xform is false)
+        k = k_modup<LOGN>;
+        g = dim3(xcd_grid(E, M));
+        b = dim3((1 << LOGN) / 16);
+    } else if (modup_xform(T, l)) {   // every digit of this level full (3 limbs), X form (launch_centered)
+        k = T.conv_b59 ? k_modup_h<LOGN, 3, true> : k_modup_h<LOGN, 3, false>;
+    } else if (T.modup_dp == 1) {   // all_b59: SEAL's 59-bit chains, compile-time lazy NTT and folded stores
+        k = T.all_b59 ? k_modup_h<LOGN, 1, true> : k_modup_h<LOGN, 1, false>;
+    } else {
+        k = k_modup_h<LOGN, 0, false>;
+    }
+    hipLaunchKernelGGL(k, g, b, 0, st, T, uniq, acoef, vcnt, ext, l, U);
 }
 
 // (b2) key inner product with the automorphism applied on the fly, lazy 128-bit over digits:
@@ -1247,9 +1230,6 @@ constexpr int kBufNT = 2;   // buffer aux: non-temporal (streamed once: the swit
 // seeds, or read from an imported key's explicit a (akey, a separate instantiation: the choice is
 // per item, so the digit loop carries no branch)
 typedef const __attribute__((address_space(4))) u64* cu64p;   // constant address space: scalar loads
-#ifndef FHS_KSIP_V6
-#define FHS_KSIP_V6 0   // 1: own digit first, the other digits branch-free -- measured slower, kept off (profiles/r06/ab_ksip_v6)
-#endif
 template <bool EXPLICIT_A>
 __device__ __forceinline__ void ks_digit(const KsOps& o, u64 x, int j, u64 seed, u64 cx, const RedU& RD, unsigned qb,
                                          Acc3& a0, Acc3& a1) {
@@ -1268,43 +1248,6 @@ __device__ __forceinline__ void ks_digits(const KsOps& o, const u64* seeds_g, u6
     // the seeds are wave-uniform and read-only: scalar loads instead of flat vector loads
     const cu64p seeds = (cu64p)seeds_g;
     Acc3 a0 = {0, 0, 0}, a1 = {0, 0, 0};
-#if FHS_KSIP_V6
-    // The digit whose limb t is the input's own (read from the input, not extended) first, then the others as
-    // j = k + (k >= jown): the unrolled body has no per-digit branch between the input and the extension, so the
-    // scheduler can issue a group's seed loads and buffer loads together (round 5: a diamond per digit and a
-    // scalar load waited on at once -- 0.61 SALU per VALU, 46 % of wave cycles ready but not issued).  The sums
-    // are exact integers, so the order of the products does not change them.
-    // wave-uniform by construction (readfirstlane: the own digit's sampler loop must not make them look divergent,
-    // which turns every digit's soffset into a waterfall loop)
-    const int jo = __builtin_amdgcn_readfirstlane(o.jown >= 0 ? o.jown : dn);
-    const int nd = __builtin_amdgcn_readfirstlane(o.jown >= 0 ? dn - 1 : dn);
-    if (o.jown >= 0) {
-        ks_digit<EXPLICIT_A>(o, bload64(o.own, o.sn8, 0), o.jown, seeds[o.jown], cx, RD, qb, a0, a1);
-        acc3_fold(c0, a0);
-        acc3_fold(c1, a1);
-    }
-    int k = 0;
-    for (; k + 4 <= nd; k += 4) {   // groups of 4 digits: the 4 seed loads issued together, then the products
-        int jj[4];
-        u64 sd[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            jj[u] = __builtin_amdgcn_readfirstlane(k + u + (k + u >= jo ? 1 : 0));
-            sd[u] = seeds[jj[u]];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            ks_digit<EXPLICIT_A>(o, bload64(o.ext, o.sn8, jj[u] * o.per_r8), jj[u], sd[u], cx, RD, qb, a0, a1);
-        if (k & 4) {   // Acc3 holds 8 products; 128-bit sums stay < 2^128 for any dnum <= 8 * 32
-            acc3_fold(c0, a0);
-            acc3_fold(c1, a1);
-        }
-    }
-    for (; k < nd; ++k) {   // < 4 left (at most 7 products since the last fold)
-        const int j = __builtin_amdgcn_readfirstlane(k + (k >= jo ? 1 : 0));
-        ks_digit<EXPLICIT_A>(o, bload64(o.ext, o.sn8, j * o.per_r8), j, seeds[j], cx, RD, qb, a0, a1);
-    }
-#else
 #pragma unroll FHS_KSIP_UNROLL
     for (int j = 0; j < dn; ++j) {
         const bool own = j == o.jown;
@@ -1315,7 +1258,6 @@ __device__ __forceinline__ void ks_digits(const KsOps& o, const u64* seeds_g, u6
             acc3_fold(c1, a1);
         }
     }
-#endif
     acc3_fold(c0, a0);
     acc3_fold(c1, a1);
 }
@@ -1676,12 +1618,32 @@ __global__ void __launch_bounds__((1 << LOGN) / 32, 4) k_moddown_h(DevTables T, 
     }
 }
 
-static size_t ks_core_bytes(const DevTables& T, int R, int U, int l) {
+// The key-switch workspace of R items over U distinct inputs at level l, stated once: acoef [U][l][N] |
+// ext [U][dn][E][N] | acc [R][2][E][N] | ycoef [R][2][P][N] | centred counts [U][dn][N] bytes, rounded up to words.
+// Word offsets from the base (vcnt's too: the words before it); `bytes` is the whole area.
+struct KsLayout {
+    size_t acoef, ext, acc, ycoef, vcnt, bytes;
+};
+static KsLayout ks_layout(const DevTables& T, int R, int U, int l) {
     const size_t N = T.N, E = l + T.P, dn = (l + T.P - 1) / T.P;
-    // acoef | ext | acc | ycoef | centred counts (bytes, rounded up to words)
-    return 8 * N * ((size_t)U * l + (size_t)U * dn * E + (size_t)R * 2 * E + (size_t)R * 2 * T.P) +
-           ((size_t)U * dn * N + 7) / 8 * 8;
+    KsLayout o;
+    o.acoef = 0;
+    o.ext = o.acoef + (size_t)U * l * N;
+    o.acc = o.ext + (size_t)U * dn * E * N;
+    o.ycoef = o.acc + (size_t)R * 2 * E * N;
+    o.vcnt = o.ycoef + (size_t)R * 2 * T.P * N;
+    o.bytes = 8 * o.vcnt + ((size_t)U * dn * N + 7) / 8 * 8;
+    return o;
 }
+struct KsBufs {
+    u64 *acoef, *ext, *acc, *ycoef;
+    unsigned char* vcnt;
+};
+static KsBufs ks_carve(const DevTables& T, u64* ws, int R, int U, int l) {
+    const KsLayout o = ks_layout(T, R, U, l);
+    return KsBufs{ws + o.acoef, ws + o.ext, ws + o.acc, ws + o.ycoef, reinterpret_cast<unsigned char*>(ws + o.vcnt)};
+}
+static size_t ks_core_bytes(const DevTables& T, int R, int U, int l) { return ks_layout(T, R, U, l).bytes; }
 // SEAL convention: every item's input gets its own decomposition (U = R) and the permuted
 // ciphertexts [R][2][l][N] follow the core workspace
 size_t keyswitch_workspace_bytes(const DevTables& T, int R, int U, int l) {
@@ -1756,85 +1718,74 @@ static hipError_t seal_permute(const DevTables& T, const KsItem* orig, int R, in
     return flush();
 }
 
-// key-switch workspace carve: acoef | ext | acc | ycoef | centred counts (ks_core_bytes)
-struct KsBufs {
-    u64 *acoef, *ext, *acc, *ycoef;
-    unsigned char* vcnt;
-};
-static KsBufs ks_carve(const DevTables& T, u64* ws, int R, int U, int l) {
-    const size_t N = T.N, E = l + T.P, dn = (l + T.P - 1) / T.P;
-    KsBufs b;
-    b.acoef = ws;
-    b.ext = b.acoef + (size_t)U * l * N;
-    b.acc = b.ext + (size_t)U * dn * E * N;
-    b.ycoef = b.acc + (size_t)R * 2 * E * N;
-    b.vcnt = reinterpret_cast<unsigned char*>(b.ycoef + (size_t)R * 2 * T.P * N);
-    return b;
-}
-// INTT + centred ModUp per distinct input, then key inner product and special-limb INTT per item;
-// leaves acc [R][2][E][N] and ycoef [R][2][P][N]
+// ---- key-switch stages: each owns its timer marks; launch_keyswitch (plain and SEAL-hoisted) and launch_bsgs
+// compose them over one KsBufs
+// INTT + centring of the U distinct inputs -> acoef, counts / X form (zflag: launch_centered's zero flag)
 template <int LOGN>
-static void ks_front(const DevTables& T, const KsItem* it, const u64* const* uniq, int R, int U, int l, u64* ws,
-                     hipStream_t st, const KTimer* tm, u64** acc_out, u64** ycoef_out) {
-    const size_t N = T.N, E = l + T.P, dn = (l + T.P - 1) / T.P;
-    u64* acoef = ws;
-    u64* ext = acoef + (size_t)U * l * N;
-    u64* acc = ext + (size_t)U * dn * E * N;
-    u64* ycoef = acc + (size_t)R * 2 * E * N;
-    unsigned char* vcnt = reinterpret_cast<unsigned char*>(ycoef + (size_t)R * 2 * T.P * N);
-    const dim3 blk((1 << LOGN) / 16);
+static void ks_intt_stage(const DevTables& T, const u64* const* uniq, int U, int l, const KsBufs& b, hipStream_t st,
+                          const KTimer* tm, unsigned* zflag = nullptr) {
     FHS_TMARK(tm, KID_KS_INTT, 1, st);
     if (ks_intt_half<LOGN>(l * U))
-        hipLaunchKernelGGL((k_ks_intt_h<LOGN>), dim3(l * U), dim3((1 << LOGN) / 32), 0, st, T, uniq, acoef, l, U);
+        hipLaunchKernelGGL((k_ks_intt_h<LOGN>), dim3(l * U), dim3((1 << LOGN) / 32), 0, st, T, uniq, b.acoef, l, U);
     else
-        hipLaunchKernelGGL((k_ks_intt<LOGN>), dim3(l * U), blk, 0, st, T, uniq, acoef, l, U);
-    launch_centered(T, acoef, vcnt, l, U, st);
+        hipLaunchKernelGGL((k_ks_intt<LOGN>), dim3(l * U), dim3((1 << LOGN) / 16), 0, st, T, uniq, b.acoef, l, U);
+    launch_centered(T, b.acoef, b.vcnt, l, U, st, zflag);
     FHS_TMARK(tm, KID_KS_INTT, 0, st);
+}
+template <int LOGN>
+static void ks_modup_stage(const DevTables& T, const u64* const* uniq, int U, int l, const KsBufs& b, hipStream_t st,
+                           const KTimer* tm) {
     FHS_TMARK(tm, KID_MODUP, 1, st);
-    launch_modup<LOGN>(T, uniq, acoef, vcnt, ext, l, U, st);
+    launch_modup<LOGN>(T, uniq, b.acoef, b.vcnt, b.ext, l, U, st);
     FHS_TMARK(tm, KID_MODUP, 0, st);
+}
+// hoisted key inner product: every limb of every item -> acc [R][2][E][N]
+static void ks_ip_stage(const DevTables& T, const KsItem* it, const u64* const* uniq, int R, int l, const KsBufs& b,
+                        hipStream_t st, const KTimer* tm) {
     FHS_TMARK(tm, KID_KS_IP, 1, st);
-    hipLaunchKernelGGL(k_ks_ip, dim3(xcd_grid((int)E, R * (int)(N >> 8))), dim3(256), 0, st, T, it, uniq, ext, acc, l, R,
+    hipLaunchKernelGGL(k_ks_ip, dim3(xcd_grid(l + T.P, R * (T.N >> 8))), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R,
                        0);
     FHS_TMARK(tm, KID_KS_IP, 0, st);
-    FHS_TMARK(tm, KID_SPECIAL_INTT, 1, st);
-    FHS_NTT_LAUNCH(k_ks_special_intt, T.P * 2 * R, dim3(T.P, 2, R), st, T, acc, ycoef, l, R);
-    FHS_TMARK(tm, KID_SPECIAL_INTT, 0, st);
-    *acc_out = acc;
-    *ycoef_out = ycoef;
 }
-
-// ModDown of the R accumulators (acc, ycoef from ks_front) into the items' outputs
+// giant-step key inner product: the special limbs per rotation, the data limbs summed over the rotations
+static void giant_ip_stage(const DevTables& T, const KsItem* it, const u64* const* uniq, int R, int l, const KsBufs& b,
+                           hipStream_t st, const KTimer* tm) {
+    const int NB = T.N >> 8;
+    FHS_TMARK(tm, KID_KS_IP, 1, st);
+    hipLaunchKernelGGL(k_ks_ip, dim3(T.P * R * NB), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R, l);
+    hipLaunchKernelGGL(k_ks_ip_sum, dim3(xcd_grid(l, NB)), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R);
+    FHS_TMARK(tm, KID_KS_IP, 0, st);
+}
+// special limbs of acc -> ycoef [R][2][P][N] (coefficient form)
 template <int LOGN>
-static hipError_t launch_moddown(const DevTables& T, const KsItem* it, u64* acc, u64* ycoef, int l, int R, hipStream_t st,
-                                 const KTimer* tm) {
+static void ks_special_intt_stage(const DevTables& T, int R, int l, const KsBufs& b, hipStream_t st, const KTimer* tm) {
+    FHS_TMARK(tm, KID_SPECIAL_INTT, 1, st);
+    FHS_NTT_LAUNCH(k_ks_special_intt, T.P * 2 * R, dim3(T.P, 2, R), st, T, b.acc, b.ycoef, l, R);
+    FHS_TMARK(tm, KID_SPECIAL_INTT, 0, st);
+}
+// ModDown of the R accumulators (acc, ycoef) into the items' outputs
+template <int LOGN>
+static hipError_t ks_moddown_stage(const DevTables& T, const KsItem* it, int R, int l, const KsBufs& b, hipStream_t st,
+                                   const KTimer* tm) {
     FHS_TMARK(tm, KID_MODDOWN, 1, st);
-    // a single key switch's ModDown at N = 32768 (few workgroups): one workgroup per half (SPLIT)
-    static const bool split_off = getenv("FHESPEAR_MODDOWN_UNSPLIT") != nullptr;
-    const bool split = LOGN == 15 && !split_off && l * 2 * R < FHS_SPLIT_MAX_WG;
-    if ((FHS_MODDOWN_HALF && LOGN >= 9) || ntt_half<LOGN>()) {
-        if (T.md_xform) {   // the special digit to its X form, then the two-product conversion
-            hipLaunchKernelGGL(k_special_x, dim3((T.N + 255) / 256, 2 * R), dim3(256), 0, st, T, ycoef, 2 * R);
-            if (T.conv_b59 && split)
-                hipLaunchKernelGGL((k_moddown_h<LOGN, true, true, true>), dim3(2 * l * 2 * R), dim3((1 << LOGN) / 32), 0,
-                                   st, T, it, acc, ycoef, l, R);
-            else if (T.conv_b59)
-                hipLaunchKernelGGL((k_moddown_h<LOGN, true, true>), dim3(l * 2 * R), dim3((1 << LOGN) / 32), 0, st, T,
-                                   it, acc, ycoef, l, R);
-            else
-                hipLaunchKernelGGL((k_moddown_h<LOGN, true>), dim3(l * 2 * R), dim3((1 << LOGN) / 32), 0, st, T, it, acc,
-                                   ycoef, l, R);
-        } else {
-            if (T.all_b59)
-                hipLaunchKernelGGL((k_moddown_h<LOGN, false, true>), dim3(l * 2 * R), dim3((1 << LOGN) / 32), 0, st, T,
-                                   it, acc, ycoef, l, R);
-            else
-                hipLaunchKernelGGL((k_moddown_h<LOGN, false>), dim3(l * 2 * R), dim3((1 << LOGN) / 32), 0, st, T, it,
-                                   acc, ycoef, l, R);
-        }
+    void (*k)(DevTables, const KsItem*, const u64*, const u64*, int, int);
+    int nwg = l * 2 * R, threads = (1 << LOGN) / 32;   // k_moddown_h
+    const bool xform = ks_uses_half(LOGN) && T.md_xform;
+    if (!ks_uses_half(LOGN)) {
+        k = k_moddown<LOGN>;
+        threads = (1 << LOGN) / 16;
+    } else if (xform && T.conv_b59 && LOGN == 15 && nwg < FHS_SPLIT_MAX_WG) {
+        // a single key switch's ModDown at N = 32768 (few workgroups): one workgroup per half (SPLIT)
+        k = k_moddown_h<LOGN, true, true, true>;
+        nwg *= 2;
+    } else if (xform) {
+        k = T.conv_b59 ? k_moddown_h<LOGN, true, true> : k_moddown_h<LOGN, true>;
     } else {
-        hipLaunchKernelGGL((k_moddown<LOGN>), dim3(l * 2 * R), dim3((1 << LOGN) / 16), 0, st, T, it, acc, ycoef, l, R);
+        k = T.all_b59 ? k_moddown_h<LOGN, false, true> : k_moddown_h<LOGN, false>;
     }
+    if (xform)   // the special digit to its X form, then the two-product conversion
+        hipLaunchKernelGGL(k_special_x, dim3((T.N + 255) / 256, 2 * R), dim3(256), 0, st, T, b.ycoef, 2 * R);
+    hipLaunchKernelGGL(k, dim3(nwg), dim3(threads), 0, st, T, it, b.acc, b.ycoef, l, R);
     FHS_TMARK(tm, KID_MODDOWN, 0, st);
     return hipGetLastError();
 }
@@ -1922,15 +1873,7 @@ hipError_t launch_keyswitch(const DevTables& T, const KsItem* items_host, int R,
         if (e == hipSuccess) e = hipMemsetAsync(sh->zflag_dev, 0, sizeof(unsigned), st);
         if (e != hipSuccess) return e;
         const KsBufs b = ks_carve(T, ws, R, U, l);
-        FHS_DISPATCH_LOGN(T.logN, {
-            FHS_TMARK(tm, KID_KS_INTT, 1, st);
-            if (ks_intt_half<LOGN>(l * U))
-                hipLaunchKernelGGL((k_ks_intt_h<LOGN>), dim3(l * U), dim3((1 << LOGN) / 32), 0, st, T, uq, b.acoef, l, U);
-            else
-                hipLaunchKernelGGL((k_ks_intt<LOGN>), dim3(l * U), dim3((1 << LOGN) / 16), 0, st, T, uq, b.acoef, l, U);
-            launch_centered(T, b.acoef, b.vcnt, l, U, st, sh->zflag_dev);
-            FHS_TMARK(tm, KID_KS_INTT, 0, st);
-        });
+        FHS_DISPATCH_LOGN(T.logN, ks_intt_stage<LOGN>(T, uq, U, l, b, st, tm, sh->zflag_dev));
         e = hipMemcpyAsync(sh->zflag_host, sh->zflag_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return e;
@@ -1940,17 +1883,10 @@ hipError_t launch_keyswitch(const DevTables& T, const KsItem* items_host, int R,
         }
         ++sh->hoisted;
         FHS_DISPATCH_LOGN(T.logN, {
-            FHS_TMARK(tm, KID_MODUP, 1, st);
-            launch_modup<LOGN>(T, uq, b.acoef, b.vcnt, b.ext, l, U, st);
-            FHS_TMARK(tm, KID_MODUP, 0, st);
-            FHS_TMARK(tm, KID_KS_IP, 1, st);
-            hipLaunchKernelGGL(k_ks_ip, dim3(xcd_grid(l + T.P, R * (int)(T.N >> 8))), dim3(256), 0, st, T, it, uq, b.ext,
-                               b.acc, l, R, 0);
-            FHS_TMARK(tm, KID_KS_IP, 0, st);
-            FHS_TMARK(tm, KID_SPECIAL_INTT, 1, st);
-            FHS_NTT_LAUNCH(k_ks_special_intt, T.P * 2 * R, dim3(T.P, 2, R), st, T, b.acc, b.ycoef, l, R);
-            FHS_TMARK(tm, KID_SPECIAL_INTT, 0, st);
-            e = launch_moddown<LOGN>(T, it, b.acc, b.ycoef, l, R, st, tm);
+            ks_modup_stage<LOGN>(T, uq, U, l, b, st, tm);
+            ks_ip_stage(T, it, uq, R, l, b, st, tm);
+            ks_special_intt_stage<LOGN>(T, R, l, b, st, tm);
+            e = ks_moddown_stage<LOGN>(T, it, R, l, b, st, tm);
         });
         if (e != hipSuccess) return e;
         return hipGetLastError();
@@ -1969,10 +1905,13 @@ hipError_t launch_keyswitch(const DevTables& T, const KsItem* items_host, int R,
     hipError_t e = upload_items(items_host, R, uniq_host, U, items_dev, sg, &it, &uq);
     if (e != hipSuccess) return e;
     hipError_t me = hipSuccess;
+    const KsBufs b = ks_carve(T, ws, R, U, l);
     FHS_DISPATCH_LOGN(T.logN, {
-        u64 *acc, *ycoef;
-        ks_front<LOGN>(T, it, uq, R, U, l, ws, st, tm, &acc, &ycoef);
-        me = launch_moddown<LOGN>(T, it, acc, ycoef, l, R, st, tm);
+        ks_intt_stage<LOGN>(T, uq, U, l, b, st, tm);
+        ks_modup_stage<LOGN>(T, uq, U, l, b, st, tm);
+        ks_ip_stage(T, it, uq, R, l, b, st, tm);
+        ks_special_intt_stage<LOGN>(T, R, l, b, st, tm);
+        me = ks_moddown_stage<LOGN>(T, it, R, l, b, st, tm);
     });
     if (me != hipSuccess) return me;
     return hipGetLastError();
@@ -1980,9 +1919,9 @@ hipError_t launch_keyswitch(const DevTables& T, const KsItem* items_host, int R,
 
 // ============================================================================ BSGS
 // inner[g] = sum_{b < G, gG+b < D} baby[b] (.) pts[gG+b]        (bg:465-476)
-// Block = 4 waves sharing one 64-coefficient slice of limb i: the slice of all G baby steps
-// (both components) is staged once in LDS, each wave then streams the diagonals of its giant
-// groups (g = wave, wave+4, ...) from HBM with lazy 128-bit accumulation.
+// Block = 16 waves (FHS_INNER_WAVES) sharing one 128-coefficient slice (64 lanes x FHS_INNER_VEC) of limb i: the
+// slice of all G baby steps (both components) is staged once in LDS, each wave then streams the diagonals of its
+// giant groups (g = wave, wave + 16, ...) from HBM with lazy 128-bit accumulation.
 // diagonal words of plaintext `p` (limb base p + i N) at this lane's coefficients: a non-temporal buffer
 // load (the limb offset and the slice offset n0 are wave-uniform: descriptor base and soffset), so no
 // 64-bit address arithmetic and no flat load (which would also wait on the LDS counter)
@@ -2198,105 +2137,65 @@ __global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_giant_final(DevTab
                                [&](int e, u64 v) { out[off + e] = submod(base[off + e], shoup(v, pinv, pinv_s, q), q); });
 }
 
-// ---- key-switch stages of the BSGS giant steps
-template <int LOGN>
-static void ks_modup_stage(const DevTables& T, const u64* const* uniq, int U, int l, const KsBufs& b, hipStream_t st,
-                           const KTimer* tm) {
-    FHS_TMARK(tm, KID_KS_INTT, 1, st);
-    if (ks_intt_half<LOGN>(l * U))
-        hipLaunchKernelGGL((k_ks_intt_h<LOGN>), dim3(l * U), dim3((1 << LOGN) / 32), 0, st, T, uniq, b.acoef, l, U);
-    else
-        hipLaunchKernelGGL((k_ks_intt<LOGN>), dim3(l * U), dim3((1 << LOGN) / 16), 0, st, T, uniq, b.acoef, l, U);
-    launch_centered(T, b.acoef, b.vcnt, l, U, st);
-    FHS_TMARK(tm, KID_KS_INTT, 0, st);
-    FHS_TMARK(tm, KID_MODUP, 1, st);
-    launch_modup<LOGN>(T, uniq, b.acoef, b.vcnt, b.ext, l, U, st);
-    FHS_TMARK(tm, KID_MODUP, 0, st);
-}
-template <int LOGN>
-static void giant_ip_stage(const DevTables& T, const KsItem* it, const u64* const* uniq, int R, int l, const KsBufs& b,
-                           hipStream_t st, const KTimer* tm) {
-    const int NB = T.N >> 8;
-    FHS_TMARK(tm, KID_KS_IP, 1, st);
-    hipLaunchKernelGGL(k_ks_ip, dim3(T.P * R * NB), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R, l);
-    hipLaunchKernelGGL(k_ks_ip_sum, dim3(xcd_grid(l, NB)), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R);
-    FHS_TMARK(tm, KID_KS_IP, 0, st);
-    FHS_TMARK(tm, KID_SPECIAL_INTT, 1, st);
-    FHS_NTT_LAUNCH(k_ks_special_intt, T.P * 2 * R, dim3(T.P, 2, R), st, T, b.acc, b.ycoef, l, R);
-    FHS_TMARK(tm, KID_SPECIAL_INTT, 0, st);
-}
-
 // core key-switch workspace of the R giant rotations, then base | convsum (2 ciphertexts)
 size_t bsgs_workspace_bytes(const DevTables& T, int R, int l) {
     return keyswitch_workspace_bytes(T, R, R, l) + 8 * (size_t)T.N * 4 * l;
 }
 
+// Dynamic LDS above 64 KiB must be opted into, once per kernel.  `each(f)` calls f on every kernel of a selector's
+// domain (null entries skipped).  `done` is set only after all of them took the attribute, so a failed attempt is
+// made again by the next call; two threads may both run the loop (setting the attribute twice is harmless).
+template <class Each>
+static hipError_t lds_opt_in(std::atomic<bool>& done, size_t bytes, Each each) {
+    if (done.load(std::memory_order_acquire)) return hipSuccess;
+    hipError_t e = hipSuccess;
+    each([&](const void* k) {
+        if (k && e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    });
+    if (e == hipSuccess) done.store(true, std::memory_order_release);
+    return e;
+}
+
 constexpr int kInnerWindow = 64;   // baby steps per k_bsgs_inner launch: [64][2][128] words = 128 KiB of LDS
-// compact diagonals (tlog 1..3; 59-bit chains: the FOLD = 16 kernels)
-template <int VEC, int WAVES, int TL>
-static void launch_inner_compact(dim3 grid, dim3 block, size_t lds, hipStream_t st, const DevTables& T,
-                                 const u64* const* baby, const u64* const* pts, int G, int Gw, int g0, int g1, int Dw,
-                                 int l, u64* inner, bool acc) {
-    if (acc)
-        hipLaunchKernelGGL((k_bsgs_inner<VEC, WAVES, 16, true, TL>), grid, block, lds, st, T, baby, pts, G, Gw, g0, g1,
-                           Dw, l, inner);
-    else
-        hipLaunchKernelGGL((k_bsgs_inner<VEC, WAVES, 16, false, TL>), grid, block, lds, st, T, baby, pts, G, Gw, g0, g1,
-                           Dw, l, inner);
+// The instantiations of k_bsgs_inner, by the run-time choices: FOLD = 16 or 8, ACC, TL = ptl in 0..3.  Compact
+// diagonals (ptl > 0; 59-bit chains) exist with FOLD = 16 only: null elsewhere.
+typedef void (*InnerFn)(DevTables, const u64* const*, const u64* const*, int, int, int, int, int, int, u64*);
+template <int VEC, int WAVES, int FOLD, int TL>
+static InnerFn inner_kernel_acc(bool acc) {
+    return acc ? k_bsgs_inner<VEC, WAVES, FOLD, true, TL> : k_bsgs_inner<VEC, WAVES, FOLD, false, TL>;
+}
+template <int VEC, int WAVES>
+static InnerFn inner_kernel(bool fold16, bool acc, int ptl) {
+    if (!fold16) return ptl == 0 ? inner_kernel_acc<VEC, WAVES, 8, 0>(acc) : nullptr;
+    switch (ptl) {
+        case 0: return inner_kernel_acc<VEC, WAVES, 16, 0>(acc);
+        case 1: return inner_kernel_acc<VEC, WAVES, 16, 1>(acc);
+        case 2: return inner_kernel_acc<VEC, WAVES, 16, 2>(acc);
+        case 3: return inner_kernel_acc<VEC, WAVES, 16, 3>(acc);
+    }
+    return nullptr;
 }
 template <int VEC, int WAVES>
 static hipError_t launch_inner_t(const DevTables& T, const u64* const* baby, const u64* const* pts, int G, int g0,
                                  int g1, int D, int l, u64* inner, hipStream_t st, int ptl) {
     constexpr int W = 64 * VEC;
-    static bool attr = false;
-    if (!attr) {   // dynamic LDS above 64 KiB must be opted into
-        for (const void* k : {reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 8, false>),
-                              reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 16, false>),
-                              reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 8, true>),
-                              reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 16, true>),
-                              reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 16, false, 1>),
-                              reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 16, true, 1>),
-                              reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 16, false, 2>),
-                              reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 16, true, 2>),
-                              reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 16, false, 3>),
-                              reinterpret_cast<const void*>(&k_bsgs_inner<VEC, WAVES, 16, true, 3>)}) {
-            hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)(kInnerWindow * 2 * W * 8));
-            if (e != hipSuccess) return e;
-        }
-        attr = true;
-    }
+    static std::atomic<bool> opted{false};
+    hipError_t e = lds_opt_in(opted, (size_t)kInnerWindow * 2 * W * 8, [](auto f) {
+        for (int fold16 = 0; fold16 < 2; ++fold16)
+            for (int acc = 0; acc < 2; ++acc)
+                for (int tl = 0; tl <= 3; ++tl)
+                    f(reinterpret_cast<const void*>(inner_kernel<VEC, WAVES>(fold16, acc, tl)));
+    });
+    if (e != hipSuccess) return e;
     if (ptl < 0 || ptl > 3 || (ptl > 0 && (T.max_qbits > 59 || VEC != 2))) return hipErrorInvalidValue;
     // G <= 64: one launch over every baby step; else windows of 64, each adding to the previous ones' sums
     for (int b0 = 0; b0 < G; b0 += kInnerWindow) {
         const int Gw = std::min(kInnerWindow, G - b0), Dw = D - b0;
         const size_t lds = (size_t)Gw * 2 * W * 8;
         const dim3 grid(T.N / W, l), block(64 * WAVES);
-        if (ptl == 1) {
-            launch_inner_compact<VEC, WAVES, 1>(grid, block, lds, st, T, baby + b0, pts + b0, G, Gw, g0, g1, Dw, l, inner,
-                                                b0 > 0);
-        } else if (ptl == 2) {
-            launch_inner_compact<VEC, WAVES, 2>(grid, block, lds, st, T, baby + b0, pts + b0, G, Gw, g0, g1, Dw, l, inner,
-                                                b0 > 0);
-        } else if (ptl == 3) {
-            launch_inner_compact<VEC, WAVES, 3>(grid, block, lds, st, T, baby + b0, pts + b0, G, Gw, g0, g1, Dw, l, inner,
-                                                b0 > 0);
-        } else if (T.max_qbits <= 59) {
-            if (b0)
-                hipLaunchKernelGGL((k_bsgs_inner<VEC, WAVES, 16, true>), grid, block, lds, st, T, baby + b0, pts + b0, G, Gw,
-                                   g0, g1, Dw, l, inner);
-            else
-                hipLaunchKernelGGL((k_bsgs_inner<VEC, WAVES, 16, false>), grid, block, lds, st, T, baby, pts, G, Gw, g0, g1,
-                                   Dw, l, inner);
-        } else {
-            if (b0)
-                hipLaunchKernelGGL((k_bsgs_inner<VEC, WAVES, 8, true>), grid, block, lds, st, T, baby + b0, pts + b0, G, Gw,
-                                   g0, g1, Dw, l, inner);
-            else
-                hipLaunchKernelGGL((k_bsgs_inner<VEC, WAVES, 8, false>), grid, block, lds, st, T, baby, pts, G, Gw, g0, g1,
-                                   Dw, l, inner);
-        }
-        hipError_t e = hipGetLastError();
+        const InnerFn k = inner_kernel<VEC, WAVES>(T.max_qbits <= 59, b0 > 0, ptl);
+        hipLaunchKernelGGL(k, grid, block, lds, st, T, baby + b0, pts + b0, G, Gw, g0, g1, Dw, l, inner);
+        e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -2400,41 +2299,31 @@ __global__ void __launch_bounds__(64 * WAVES) k_dot_tensor(DevTables T, const u6
         }
     }
 }
+// The instantiations of k_dot_tensor, by the run-time choices: FOLD = 16 or 8, ACC
+typedef void (*DotFn)(DevTables, const u64* const*, const u64* const*, int, int, int, int, u64*);
+template <int VEC, int WAVES>
+static DotFn dot_kernel(bool fold16, bool acc) {
+    if (fold16) return acc ? k_dot_tensor<VEC, WAVES, 16, true> : k_dot_tensor<VEC, WAVES, 16, false>;
+    return acc ? k_dot_tensor<VEC, WAVES, 8, true> : k_dot_tensor<VEC, WAVES, 8, false>;
+}
 template <int VEC, int WAVES>
 static hipError_t launch_dot_t(const DevTables& T, const u64* const* q, const u64* const* db, int J, int C, int l, u64* out,
                                hipStream_t st) {
     constexpr int W = 64 * VEC;
-    static bool attr = false;
-    if (!attr) {   // dynamic LDS above 64 KiB must be opted into
-        for (const void* k : {reinterpret_cast<const void*>(&k_dot_tensor<VEC, WAVES, 8, false>),
-                              reinterpret_cast<const void*>(&k_dot_tensor<VEC, WAVES, 8, true>),
-                              reinterpret_cast<const void*>(&k_dot_tensor<VEC, WAVES, 16, false>),
-                              reinterpret_cast<const void*>(&k_dot_tensor<VEC, WAVES, 16, true>)}) {
-            hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)(kDotWindowMax * 2 * W * 8));
-            if (e != hipSuccess) return e;
-        }
-        attr = true;
-    }
+    static std::atomic<bool> opted{false};
+    hipError_t e = lds_opt_in(opted, (size_t)kDotWindowMax * 2 * W * 8, [](auto f) {
+        for (int fold16 = 0; fold16 < 2; ++fold16)
+            for (int acc = 0; acc < 2; ++acc) f(reinterpret_cast<const void*>(dot_kernel<VEC, WAVES>(fold16, acc)));
+    });
+    if (e != hipSuccess) return e;
     // J <= 64: one launch over every term; else windows of 64, each adding to the previous ones' reduced sums
     for (int j0 = 0; j0 < J; j0 += kDotWindowMax) {
         const int Jw = std::min(kDotWindowMax, J - j0);
         const size_t lds = (size_t)Jw * 2 * W * 8;
         const dim3 grid(T.N / W, l), block(64 * WAVES);
-        if (T.max_qbits <= 59) {
-            if (j0)
-                hipLaunchKernelGGL((k_dot_tensor<VEC, WAVES, 16, true>), grid, block, lds, st, T, q + j0, db + j0, J, Jw, C, l,
-                                   out);
-            else
-                hipLaunchKernelGGL((k_dot_tensor<VEC, WAVES, 16, false>), grid, block, lds, st, T, q, db, J, Jw, C, l, out);
-        } else {
-            if (j0)
-                hipLaunchKernelGGL((k_dot_tensor<VEC, WAVES, 8, true>), grid, block, lds, st, T, q + j0, db + j0, J, Jw, C, l,
-                                   out);
-            else
-                hipLaunchKernelGGL((k_dot_tensor<VEC, WAVES, 8, false>), grid, block, lds, st, T, q, db, J, Jw, C, l, out);
-        }
-        hipError_t e = hipGetLastError();
+        const DotFn k = dot_kernel<VEC, WAVES>(T.max_qbits <= 59, j0 > 0);
+        hipLaunchKernelGGL(k, grid, block, lds, st, T, q + j0, db + j0, J, Jw, C, l, out);
+        e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -2504,8 +2393,10 @@ hipError_t launch_bsgs(const DevTables& T, const u64* const* baby_dev, const u64
     u64* convsum = base + 2 * S;
     FHS_DISPATCH_LOGN(T.logN, {
         const KsBufs b = ks_carve(T, ws, R, R, l);
+        ks_intt_stage<LOGN>(T, uq, R, l, b, st, tm);
         ks_modup_stage<LOGN>(T, uq, R, l, b, st, tm);
-        giant_ip_stage<LOGN>(T, it, uq, R, l, b, st, tm);
+        giant_ip_stage(T, it, uq, R, l, b, st, tm);
+        ks_special_intt_stage<LOGN>(T, R, l, b, st, tm);
         FHS_TMARK(tm, KID_GIANT_SUM, 1, st);
         hipLaunchKernelGGL(k_giant_sum, dim3((T.N + 255) / 256, 2, (l + FHS_GSUM_ICH - 1) / FHS_GSUM_ICH), dim3(256), 0,
                            st, T, b.acc, b.ycoef, inner, base, convsum, l, R);
