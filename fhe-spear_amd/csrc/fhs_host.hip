@@ -314,6 +314,7 @@ struct fhs_context {
     std::set<const void*> pending_refs;   // inputs and outputs of queued rotations (destroy must flush)
     std::set<const void*> pending_outs;   // outputs of queued rotations (a consumer must flush)
     int debug_fail_flushes = 0;           // fhs_debug_fail_next_flushes (testing hook)
+    int debug_fail_alloc = -1;            // fhs_debug_fail_alloc (testing hook): dalloc calls left before the failure
     std::vector<std::complex<double>> fft_w;   // exp(2 pi i k / N), k < N
     std::vector<std::complex<double>> dec_twist;   // (cos, sin)(pi k / N), k < N
     std::vector<uint64_t> slot_index;          // (5^j mod 2N - 1)/2, j < N/2
@@ -462,6 +463,7 @@ static const uint64_t* key_akey(const fhs_context* c, const uint64_t* key) {
 }
 static void drop_seal_corr(fhs_context* c, const uint64_t* key);
 static void free_key(fhs_context* c, uint64_t* key) {
+    if (!key) return;
     drop_seal_corr(c, key);
     auto it = c->key_a.find(key);
     if (it != c->key_a.end()) {
@@ -520,6 +522,7 @@ static void evict_cold(fhs_context* c, size_t keep) {
     for (void* p : victims) (void)hipFree(p);
 }
 static hipError_t dalloc(fhs_context* c, uint64_t** p, size_t bytes) {
+    if (c->debug_fail_alloc >= 0 && c->debug_fail_alloc-- == 0) return hipErrorOutOfMemory;
     bytes = bytes ? bytes : 8;
     c->size_tick[bytes] = ++c->cache_tick;
     auto it = c->free_blocks.find(bytes);
@@ -555,6 +558,111 @@ static void dfree(fhs_context* c, void* p, size_t bytes) {
     c->size_tick[bytes] = ++c->cache_tick;
     if (c->cached_bytes > c->cache_cap) evict_cold(c, bytes);
 }
+// A device temporary owned by a scope: alloc() takes a block (dalloc) and remembers its size, the destructor
+// returns it to the context's cache (dfree) -- on every way out of the scope, in stream order, without a
+// synchronisation.  Declare it before the launches that use it: it must outlive their enqueueing.
+struct DevTmp {
+    fhs_context* c;
+    uint64_t* p = nullptr;
+    size_t bytes = 0;
+    explicit DevTmp(fhs_context* c_) : c(c_) {}
+    DevTmp(const DevTmp&) = delete;
+    DevTmp& operator=(const DevTmp&) = delete;
+    DevTmp(DevTmp&& o) noexcept : c(o.c), p(o.p), bytes(o.bytes) { o.p = nullptr; }
+    ~DevTmp() { dfree(c, p, bytes); }
+    hipError_t alloc(size_t n) {
+        const hipError_t e = dalloc(c, &p, n);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    template <class T = uint64_t>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
+// A switching key under construction: free_key (the key, its imported a_j, its SEAL corrections) unless released
+struct KeyTmp {
+    fhs_context* c;
+    uint64_t* p = nullptr;
+    explicit KeyTmp(fhs_context* c_) : c(c_) {}
+    KeyTmp(const KeyTmp&) = delete;
+    KeyTmp& operator=(const KeyTmp&) = delete;
+    ~KeyTmp() { free_key(c, p); }
+    hipError_t alloc() { return dalloc(c, &p, 8 * key_words(c)); }
+    uint64_t* release() {
+        uint64_t* k = p;
+        p = nullptr;
+        return k;
+    }
+};
+static void destroy_obj(fhs_plaintext* p) { fhs_plaintext_destroy(p); }
+static void destroy_obj(fhs_ciphertext* p) { fhs_ciphertext_destroy(p); }
+static void destroy_obj(fhs_secret_key* p) { fhs_secret_key_destroy(p); }
+static void destroy_obj(fhs_public_key* p) { fhs_public_key_destroy(p); }
+static void destroy_obj(fhs_relin_key* p) { fhs_relin_key_destroy(p); }
+static void destroy_obj(fhs_galois_keys* p) { fhs_galois_keys_destroy(p); }
+// Owning handle of a library object on its way to the caller: destroyed by the object's own destroy function (its
+// device blocks back to the cache, its context reference dropped) unless released into *out on success.
+template <class Obj>
+struct Own {
+    Obj* p = nullptr;
+    Own() = default;
+    explicit Own(Obj* x) : p(x) {}
+    Own(const Own&) = delete;
+    Own& operator=(const Own&) = delete;
+    Own(Own&& o) noexcept : p(o.p) { o.p = nullptr; }
+    Own& operator=(Own&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p;
+            o.p = nullptr;
+        }
+        return *this;
+    }
+    ~Own() { reset(); }
+    void reset() {
+        if (p) destroy_obj(p);
+        p = nullptr;
+    }
+    Obj* release() {
+        Obj* x = p;
+        p = nullptr;
+        return x;
+    }
+    Obj* operator->() const { return p; }
+};
+using Ct = Own<fhs_ciphertext>;
+using Pt = Own<fhs_plaintext>;
+// A key object under construction holds its context reference from the start, so its destroy function undoes all
+// of a half-built one (null device pointers are skipped)
+template <class Obj>
+static Own<Obj> adopt_key(Obj* fresh) {
+    ctx_retain(fresh->ctx);
+    return Own<Obj>(fresh);
+}
+// Output array of a batch creator: cleared on entry; if the call fails part-way (e.g. device OOM,
+// which bg:1164-1170 catches to fall back to on-the-fly encoding) the plaintexts already created
+// are destroyed and their slots reset to null, so a failed batch leaves no HBM behind.
+template <class Obj>
+struct BatchOutT {
+    Obj** outs;
+    size_t n;
+    bool kept = false;
+    BatchOutT(Obj** o, size_t count) : outs(o), n(o ? count : 0) {
+        for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    }
+    fhs_status keep(fhs_status st) {
+        kept = st == FHS_OK;
+        return st;
+    }
+    ~BatchOutT() {
+        if (kept) return;
+        for (size_t i = 0; i < n; ++i)
+            if (outs[i]) {
+                destroy_obj(outs[i]);
+                outs[i] = nullptr;
+            }
+    }
+};
+using BatchOut = BatchOutT<fhs_plaintext>;
 
 static hipError_t scratch(fhs_context* c, int slot, size_t bytes, uint64_t** p) {
     if (bytes > c->scr_bytes[slot]) {
@@ -676,6 +784,19 @@ static hipError_t pt_dense(fhs_context* c, const fhs_plaintext* cpt, const uint6
 #define PT_DENSE(var, pt, where)        \
     const uint64_t* var = nullptr;      \
     HIPCHK(pt_dense(c, (pt), &var), where)
+// A new result object held by `var` (Own): released into *out by the caller once everything has been enqueued
+#define NEW_CT(var, ...)                                              \
+    Ct var;                                                           \
+    do {                                                              \
+        fhs_status _ns = new_ct(c, __VA_ARGS__, &var.p);              \
+        if (_ns != FHS_OK) return _ns;                                \
+    } while (0)
+#define NEW_PT(var, ...)                                              \
+    Pt var;                                                           \
+    do {                                                              \
+        fhs_status _ns = new_pt(c, __VA_ARGS__, &var.p);              \
+        if (_ns != FHS_OK) return _ns;                                \
+    } while (0)
 
 // ---------------------------------------------------------------- timing events
 // A pool of timing events per device: hipEventCreate can take milliseconds now and then (it may
@@ -832,26 +953,25 @@ static hipError_t seal_prepare(fhs_context* c, std::vector<KsItem>& items, int l
     for (const KsItem& it : items)
         if (it.elt != 1 && !c->seal_corr.count({it.key, l})) need += seal_corr_bytes(c, l);
     if (need && c->seal_corr_bytes + need > cap) drop_seal_corr(c, nullptr);
-    uint64_t* mask = nullptr;
+    DevTmp mask(c);
     for (KsItem& it : items) {
         if (it.elt == 1) continue;
         auto f = c->seal_corr.find({it.key, l});
         if (f == c->seal_corr.end()) {
-            if (!mask && (e = dalloc(c, &mask, 8ull * c->K * c->N)) != hipSuccess) break;
+            if (!mask.p && (e = mask.alloc(8ull * c->K * c->N)) != hipSuccess) return e;
             uint64_t* corr = nullptr;
-            if ((e = dalloc(c, &corr, seal_corr_bytes(c, l))) != hipSuccess) break;
-            e = fhs::launch_seal_corr(c->T, it.key, it.akey, it.elt, l, mask, corr, c->st);
-            if (e != hipSuccess) {
-                dfree(c, corr, seal_corr_bytes(c, l));
-                break;
-            }
-            f = c->seal_corr.emplace(std::make_pair(it.key, l), corr).first;
+            if ((e = dalloc(c, &corr, seal_corr_bytes(c, l))) != hipSuccess) return e;
+            f = c->seal_corr.emplace(std::make_pair(it.key, l), corr).first;   // the key's from here (drop_seal_corr)
             c->seal_corr_bytes += seal_corr_bytes(c, l);
+            e = fhs::launch_seal_corr(c->T, it.key, it.akey, it.elt, l, mask.p, corr, c->st);
+            if (e != hipSuccess) {
+                drop_seal_corr(c, it.key);   // not computed: never handed to a later flush
+                return e;
+            }
         }
         it.corr = f->second;
     }
-    if (mask) dfree(c, mask, 8ull * c->K * c->N);
-    return e;
+    return hipSuccess;
 }
 
 // ---------------------------------------------------------------- deferred rotations
@@ -1369,13 +1489,11 @@ extern "C" fhs_status fhs_secret_key_create(fhs_context* c, const uint8_t* key32
     }
     uint64_t ctr0 = 0;   // stream ids carry 40 counter bits: a random start below 2^39 leaves 2^39 encryptions
     if (!parity_rng() && !os_random(&ctr0, sizeof ctr0)) return fail(FHS_ERR_INVALID, "secret_key: /dev/urandom unavailable");
-    auto* sk = new fhs_secret_key{c, nullptr, K, ctr0 & ((1ull << 39) - 1)};
-    hipError_t e = dalloc(c, &sk->s, 8ull * c->K * c->N);
-    if (e != hipSuccess) { delete sk; return hip_fail(e, "secret key"); }
-    e = sample_small_ntt(c, fhs::SAMPLE_TERNARY, sk->key, stream_id(ST_SECRET, 0, 0), sk->s, c->K);
-    if (e != hipSuccess) { delete sk; return hip_fail(e, "secret key sampling"); }
-    ctx_retain(c);
-    *out = sk;
+    auto sk = adopt_key(new fhs_secret_key{c, nullptr, K, ctr0 & ((1ull << 39) - 1)});
+    HIPCHK(dalloc(c, &sk->s, 8ull * c->K * c->N), "secret key");
+    HIPCHK(sample_small_ntt(c, fhs::SAMPLE_TERNARY, sk->key, stream_id(ST_SECRET, 0, 0), sk->s, c->K),
+           "secret key sampling");
+    *out = sk.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_secret_key_destroy(fhs_secret_key* sk) {
@@ -1389,28 +1507,25 @@ extern "C" fhs_status fhs_secret_key_destroy(fhs_secret_key* sk) {
 
 static fhs_status gen_switch_key(fhs_context* c, const PrfKey& K, uint64_t base, const uint64_t* s, const uint64_t* snew,
                                  uint64_t** key_out) {
-    uint64_t* key = nullptr;
-    hipError_t e = dalloc(c, &key, 8 * key_words(c));
-    if (e != hipSuccess) return hip_fail(e, "switching key");
+    KeyTmp key(c);
+    HIPCHK(key.alloc(), "switching key");
     const size_t S = (size_t)c->K * c->N;
-    uint64_t* tmp = nullptr;   // e | a
-    e = dalloc(c, &tmp, 16 * S);
-    if (e != hipSuccess) { dfree(c, key, 8 * key_words(c)); return hip_fail(e, "switching key"); }
-    uint64_t* ebuf = tmp;
-    uint64_t* abuf = tmp + S;
+    DevTmp tmp(c);   // e | a
+    HIPCHK(tmp.alloc(16 * S), "switching key");
+    uint64_t* ebuf = tmp.p;
+    uint64_t* abuf = tmp.p + S;
     std::vector<uint64_t> seeds(c->dnum);
-    for (int j = 0; j < c->dnum && e == hipSuccess; ++j) {
+    for (int j = 0; j < c->dnum; ++j) {
         seeds[j] = prf_u64(K, base | (uint64_t)(2 * j));   // public seed of a_j: a PRF output
-        e = fhs::launch_sample(c->T, fhs::SAMPLE_SEEDED, K, seeds[j], abuf, c->K, c->st);
-        if (e == hipSuccess) e = sample_small_ntt(c, fhs::SAMPLE_CBD, K, base | (uint64_t)(2 * j + 1), ebuf, c->K);
-        if (e == hipSuccess) e = fhs::launch_switch_key_assemble(c->T, key + (size_t)j * S, abuf, ebuf, s, snew, j, c->st);
+        HIPCHK(fhs::launch_sample(c->T, fhs::SAMPLE_SEEDED, K, seeds[j], abuf, c->K, c->st), "switching key generation");
+        HIPCHK(sample_small_ntt(c, fhs::SAMPLE_CBD, K, base | (uint64_t)(2 * j + 1), ebuf, c->K), "switching key generation");
+        HIPCHK(fhs::launch_switch_key_assemble(c->T, key.p + (size_t)j * S, abuf, ebuf, s, snew, j, c->st),
+               "switching key generation");
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(key + (size_t)c->dnum * S, seeds.data(), 8 * seeds.size(),
-                                            hipMemcpyHostToDevice, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);   // `seeds` is a host temporary
-    dfree(c, tmp, 16 * S);
-    if (e != hipSuccess) { dfree(c, key, 8 * key_words(c)); return hip_fail(e, "switching key generation"); }
-    *key_out = key;
+    HIPCHK(hipMemcpyAsync(key.p + (size_t)c->dnum * S, seeds.data(), 8 * seeds.size(), hipMemcpyHostToDevice, c->st),
+           "switching key generation");
+    HIPCHK(hipStreamSynchronize(c->st), "switching key generation");   // `seeds` is a host temporary
+    *key_out = key.release();
     return FHS_OK;
 }
 // [dnum][2][K][N] with the a_j regenerated from their seeds (the oracle's layout)
@@ -1430,32 +1545,29 @@ static fhs_status export_switch_key(fhs_context* c, const uint64_t* key, uint64_
     HIPCHK(hipMemcpyAsync(seeds.data(), key + (size_t)c->dnum * S, 8 * seeds.size(), hipMemcpyDeviceToHost, c->st),
            "key export");
     HIPCHK(hipStreamSynchronize(c->st), "key export");
-    uint64_t* full = nullptr;
-    HIPCHK(dalloc(c, &full, 8 * key_words_full(c)), "key export");
-    hipError_t e = hipSuccess;
-    for (int j = 0; j < c->dnum && e == hipSuccess; ++j) {
-        e = hipMemcpyAsync(full + (size_t)j * 2 * S, key + (size_t)j * S, 8 * S, hipMemcpyDeviceToDevice, c->st);
-        if (e == hipSuccess) e = fhs::launch_sample(c->T, fhs::SAMPLE_SEEDED, PrfKey{}, seeds[j], full + ((size_t)j * 2 + 1) * S, c->K, c->st);
+    DevTmp full(c);
+    HIPCHK(full.alloc(8 * key_words_full(c)), "key export");
+    for (int j = 0; j < c->dnum; ++j) {
+        HIPCHK(hipMemcpyAsync(full.p + (size_t)j * 2 * S, key + (size_t)j * S, 8 * S, hipMemcpyDeviceToDevice, c->st),
+               "key export");
+        HIPCHK(fhs::launch_sample(c->T, fhs::SAMPLE_SEEDED, PrfKey{}, seeds[j], full.p + ((size_t)j * 2 + 1) * S, c->K,
+                                  c->st), "key export");
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(host, full, 8 * key_words_full(c), hipMemcpyDeviceToHost, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-    dfree(c, full, 8 * key_words_full(c));
-    if (e != hipSuccess) return hip_fail(e, "key export");
+    HIPCHK(hipMemcpyAsync(host, full.p, 8 * key_words_full(c), hipMemcpyDeviceToHost, c->st), "key export");
+    HIPCHK(hipStreamSynchronize(c->st), "key export");
     return FHS_OK;
 }
 
 extern "C" fhs_status fhs_gen_relin_key(fhs_context* c, fhs_secret_key* sk, fhs_relin_key** out) {
     ENTER(c);
     if (!sk || !out) return fail(FHS_ERR_INVALID, "null argument");
-    uint64_t* s2 = nullptr;
-    HIPCHK(dalloc(c, &s2, 8ull * c->K * c->N), "relin key");
-    HIPCHK(fhs::launch_key_prod(c->T, sk->s, sk->s, s2, c->K, c->st), "relin key");
-    auto* rk = new fhs_relin_key{c, nullptr};
-    fhs_status s = gen_switch_key(c, sk->key, stream_id(ST_RELIN, 0, 0), sk->s, s2, &rk->key);
-    dfree(c, s2, 8ull * c->K * c->N);
-    if (s != FHS_OK) { delete rk; return s; }
-    ctx_retain(c);
-    *out = rk;
+    DevTmp s2(c);
+    HIPCHK(s2.alloc(8ull * c->K * c->N), "relin key");
+    HIPCHK(fhs::launch_key_prod(c->T, sk->s, sk->s, s2.p, c->K, c->st), "relin key");
+    auto rk = adopt_key(new fhs_relin_key{c, nullptr});
+    fhs_status s = gen_switch_key(c, sk->key, stream_id(ST_RELIN, 0, 0), sk->s, s2.p, &rk->key);
+    if (s != FHS_OK) return s;
+    *out = rk.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_relin_key_destroy(fhs_relin_key* rk) {
@@ -1472,33 +1584,18 @@ extern "C" fhs_status fhs_create_galois_keys(fhs_context* c, fhs_secret_key* sk,
     ENTER(c);
     if (!sk || !out) return fail(FHS_ERR_INVALID, "null argument");
     std::vector<uint64_t> list = (elts && n > 0) ? std::vector<uint64_t>(elts, elts + n) : c->elts;
-    auto* gk = new fhs_galois_keys{c, {}};
-    uint64_t* sn = nullptr;
-    hipError_t e = dalloc(c, &sn, 8ull * c->K * c->N);
-    if (e != hipSuccess) { delete gk; return hip_fail(e, "galois keys"); }
+    auto gk = adopt_key(new fhs_galois_keys{c, {}});
+    DevTmp sn(c);
+    HIPCHK(sn.alloc(8ull * c->K * c->N), "galois keys");
     for (uint64_t elt : list) {
         if (gk->keys.count(elt)) continue;
-        if ((elt & 1) == 0 || elt >= 2 * c->N) { e = hipErrorInvalidValue; break; }
-        e = fhs::launch_galois_perm(c->T, sk->s, sn, c->K, elt, c->st);
-        if (e != hipSuccess) break;
-        uint64_t* key = nullptr;
-        fhs_status s = gen_switch_key(c, sk->key, stream_id(ST_GALOIS, elt, 0), sk->s, sn, &key);
-        if (s != FHS_OK) {
-            dfree(c, sn, 8ull * c->K * c->N);
-            for (auto& kv : gk->keys) free_key(c, kv.second);
-            delete gk;
-            return s;
-        }
-        gk->keys[elt] = key;
+        if ((elt & 1) == 0 || elt >= 2 * c->N) return hip_fail(hipErrorInvalidValue, "galois key generation");
+        HIPCHK(fhs::launch_galois_perm(c->T, sk->s, sn.p, c->K, elt, c->st), "galois key generation");
+        // straight into its slot (null until the key is complete; the destroy function skips a null one)
+        fhs_status s = gen_switch_key(c, sk->key, stream_id(ST_GALOIS, elt, 0), sk->s, sn.p, &gk->keys[elt]);
+        if (s != FHS_OK) return s;
     }
-    dfree(c, sn, 8ull * c->K * c->N);
-    if (e != hipSuccess) {
-        for (auto& kv : gk->keys) free_key(c, kv.second);
-        delete gk;
-        return hip_fail(e, "galois key generation");
-    }
-    ctx_retain(c);
-    *out = gk;
+    *out = gk.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_galois_keys_destroy(fhs_galois_keys* gk) {
@@ -1557,58 +1654,43 @@ static fhs_status import_switch_key(fhs_context* c, const uint64_t* host, uint64
     for (int j = 0; j < 2 * c->dnum; ++j)
         if (!canonical_limbs(c, host + (size_t)j * S, c->K, 0))
             return fail(FHS_ERR_INVALID, "key import: residues must be canonical (< q_i) in [dnum][2][K][N] order");
-    uint64_t *key = nullptr, *a = nullptr;
-    HIPCHK(dalloc(c, &key, 8 * key_words(c)), "key import");
-    hipError_t e = dalloc(c, &a, 8ull * c->dnum * S);
-    if (e != hipSuccess) { dfree(c, key, 8 * key_words(c)); return hip_fail(e, "key import"); }
-    for (int j = 0; j < c->dnum && e == hipSuccess; ++j) {
-        e = hipMemcpyAsync(key + (size_t)j * S, host + (size_t)j * 2 * S, 8 * S, hipMemcpyHostToDevice, c->st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(a + (size_t)j * S, host + ((size_t)j * 2 + 1) * S, 8 * S, hipMemcpyHostToDevice, c->st);
+    KeyTmp key(c);
+    HIPCHK(key.alloc(), "key import");
+    uint64_t* a = nullptr;
+    HIPCHK(dalloc(c, &a, 8ull * c->dnum * S), "key import");
+    c->key_a[key.p] = a;   // from here free_key releases the pair
+    for (int j = 0; j < c->dnum; ++j) {
+        HIPCHK(hipMemcpyAsync(key.p + (size_t)j * S, host + (size_t)j * 2 * S, 8 * S, hipMemcpyHostToDevice, c->st),
+               "key import");
+        HIPCHK(hipMemcpyAsync(a + (size_t)j * S, host + ((size_t)j * 2 + 1) * S, 8 * S, hipMemcpyHostToDevice, c->st),
+               "key import");
     }
-    if (e == hipSuccess) e = hipMemsetAsync(key + (size_t)c->dnum * S, 0, 8 * c->dnum, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);   // pageable host source
-    if (e != hipSuccess) {
-        dfree(c, a, 8ull * c->dnum * S);
-        dfree(c, key, 8 * key_words(c));
-        return hip_fail(e, "key import");
-    }
-    c->key_a[key] = a;
-    *key_out = key;
+    HIPCHK(hipMemsetAsync(key.p + (size_t)c->dnum * S, 0, 8 * c->dnum, c->st), "key import");
+    HIPCHK(hipStreamSynchronize(c->st), "key import");   // pageable host source
+    *key_out = key.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_galois_keys_import(fhs_context* c, const uint64_t* elts, int n, const uint64_t* host,
                                              fhs_galois_keys** out) {
     ENTER(c);
     if (!elts || n < 1 || !host || !out) return fail(FHS_ERR_INVALID, "galois_keys_import: bad args");
-    auto* gk = new fhs_galois_keys{c, {}};
+    auto gk = adopt_key(new fhs_galois_keys{c, {}});
     for (int k = 0; k < n; ++k) {
-        if ((elts[k] & 1) == 0 || elts[k] >= 2 * c->N || gk->keys.count(elts[k])) {
-            for (auto& kv : gk->keys) free_key(c, kv.second);
-            delete gk;
+        if ((elts[k] & 1) == 0 || elts[k] >= 2 * c->N || gk->keys.count(elts[k]))
             return fail(FHS_ERR_INVALID, "galois_keys_import: invalid or repeated galois element");
-        }
-        uint64_t* key = nullptr;
-        fhs_status s = import_switch_key(c, host + (size_t)k * key_words_full(c), &key);
-        if (s != FHS_OK) {
-            for (auto& kv : gk->keys) free_key(c, kv.second);
-            delete gk;
-            return s;
-        }
-        gk->keys[elts[k]] = key;
+        fhs_status s = import_switch_key(c, host + (size_t)k * key_words_full(c), &gk->keys[elts[k]]);
+        if (s != FHS_OK) return s;
     }
-    ctx_retain(c);
-    *out = gk;
+    *out = gk.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_relin_key_import(fhs_context* c, const uint64_t* host, fhs_relin_key** out) {
     ENTER(c);
     if (!host || !out) return fail(FHS_ERR_INVALID, "null argument");
-    auto* rk = new fhs_relin_key{c, nullptr};
+    auto rk = adopt_key(new fhs_relin_key{c, nullptr});
     fhs_status s = import_switch_key(c, host, &rk->key);
-    if (s != FHS_OK) { delete rk; return s; }
-    ctx_retain(c);
-    *out = rk;
+    if (s != FHS_OK) return s;
+    *out = rk.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_secret_key_import(fhs_context* c, const uint64_t* host, fhs_secret_key** out) {
@@ -1617,17 +1699,11 @@ extern "C" fhs_status fhs_secret_key_import(fhs_context* c, const uint64_t* host
     if (!canonical_limbs(c, host, c->K, 0)) return fail(FHS_ERR_INVALID, "secret_key_import: residues must be < q_i");
     PrfKey K{};
     if (!os_random(K.k, sizeof(K.k))) return fail(FHS_ERR_INVALID, "secret_key_import: /dev/urandom unavailable");
-    auto* sk = new fhs_secret_key{c, nullptr, K, 0};   // fresh encryption randomness
-    hipError_t e = dalloc(c, &sk->s, 8ull * c->K * c->N);
-    if (e == hipSuccess) e = hipMemcpyAsync(sk->s, host, 8ull * c->K * c->N, hipMemcpyHostToDevice, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-    if (e != hipSuccess) {
-        if (sk->s) dfree(c, sk->s, 8ull * c->K * c->N);
-        delete sk;
-        return hip_fail(e, "secret_key_import");
-    }
-    ctx_retain(c);
-    *out = sk;
+    auto sk = adopt_key(new fhs_secret_key{c, nullptr, K, 0});   // fresh encryption randomness
+    HIPCHK(dalloc(c, &sk->s, 8ull * c->K * c->N), "secret_key_import");
+    HIPCHK(hipMemcpyAsync(sk->s, host, 8ull * c->K * c->N, hipMemcpyHostToDevice, c->st), "secret_key_import");
+    HIPCHK(hipStreamSynchronize(c->st), "secret_key_import");
+    *out = sk.release();
     return FHS_OK;
 }
 // key-switch convention of the context (fhs_kernels.h DevTables::ks_seal)
@@ -1661,7 +1737,7 @@ extern "C" fhs_status fhs_secret_key_export(fhs_context* c, const fhs_secret_key
 extern "C" fhs_status fhs_gen_public_key(fhs_context* c, fhs_secret_key* sk, fhs_public_key** out) {
     ENTER(c);
     if (!sk || !out) return fail(FHS_ERR_INVALID, "null argument");
-    auto* pk = new fhs_public_key{c, nullptr, PrfKey{}, 1ull << 20};
+    auto pk = adopt_key(new fhs_public_key{c, nullptr, PrfKey{}, 1ull << 20});
     // rng = 256 PRF bits of stream (ST_PK_RNG, generation): two public keys of one secret key never
     // share encryption masks (their key material is the same, so shared masks would reveal m1 - m2)
     const uint64_t gen = sk->pk_gen++;
@@ -1673,25 +1749,19 @@ extern "C" fhs_status fhs_gen_public_key(fhs_context* c, fhs_secret_key* sk, fhs
     }
     if (!parity_rng()) {   // fresh bits: the same secret key recreated elsewhere never repeats a mask stream
         PrfKey nonce{};
-        if (!os_random(nonce.k, sizeof nonce.k)) { delete pk; return fail(FHS_ERR_INVALID, "public key: /dev/urandom unavailable"); }
+        if (!os_random(nonce.k, sizeof nonce.k)) return fail(FHS_ERR_INVALID, "public key: /dev/urandom unavailable");
         for (int w = 0; w < 8; ++w) pk->rng.k[w] ^= nonce.k[w];
     }
     const size_t S = (size_t)c->L0 * c->N;
-    hipError_t e = dalloc(c, &pk->pk, 16 * S);
-    if (e != hipSuccess) { delete pk; return hip_fail(e, "public key"); }
-    uint64_t* eb = nullptr;
-    e = dalloc(c, &eb, 8 * S);
-    if (e == hipSuccess)
-        e = fhs::launch_sample(c->T, fhs::SAMPLE_UNIFORM, sk->key, stream_id(ST_PUBKEY, 0, 0), pk->pk + S, c->L0, c->st);
-    if (e == hipSuccess)
-        e = sample_small_ntt(c, fhs::SAMPLE_CBD, sk->key, stream_id(ST_PUBKEY, 0, 1), eb, c->L0);
-    if (e == hipSuccess)
-        e = fhs::launch_encrypt_combine(c->T, 0, pk->pk, pk->pk + S, sk->s, nullptr, nullptr, eb, nullptr, nullptr,
-                                        c->L0, c->st);
-    dfree(c, eb, 8 * S);
-    if (e != hipSuccess) { dfree(c, pk->pk, 16 * S); delete pk; return hip_fail(e, "public key generation"); }
-    ctx_retain(c);
-    *out = pk;
+    HIPCHK(dalloc(c, &pk->pk, 16 * S), "public key");
+    DevTmp eb(c);
+    HIPCHK(eb.alloc(8 * S), "public key generation");
+    HIPCHK(fhs::launch_sample(c->T, fhs::SAMPLE_UNIFORM, sk->key, stream_id(ST_PUBKEY, 0, 0), pk->pk + S, c->L0, c->st),
+           "public key generation");
+    HIPCHK(sample_small_ntt(c, fhs::SAMPLE_CBD, sk->key, stream_id(ST_PUBKEY, 0, 1), eb.p, c->L0), "public key generation");
+    HIPCHK(fhs::launch_encrypt_combine(c->T, 0, pk->pk, pk->pk + S, sk->s, nullptr, nullptr, eb.p, nullptr, nullptr,
+                                       c->L0, c->st), "public key generation");
+    *out = pk.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_public_key_destroy(fhs_public_key* pk) {
@@ -1752,33 +1822,6 @@ extern "C" fhs_status fhs_plaintext_destroy(fhs_plaintext* pt) {
     ctx_release(c);
     return FHS_OK;
 }
-// Output array of a batch creator: cleared on entry; if the call fails part-way (e.g. device OOM,
-// which bg:1164-1170 catches to fall back to on-the-fly encoding) the plaintexts already created
-// are destroyed and their slots reset to null, so a failed batch leaves no HBM behind.
-static void destroy_obj(fhs_plaintext* p) { fhs_plaintext_destroy(p); }
-static void destroy_obj(fhs_ciphertext* p) { fhs_ciphertext_destroy(p); }
-template <class Obj>
-struct BatchOutT {
-    Obj** outs;
-    size_t n;
-    bool kept = false;
-    BatchOutT(Obj** o, size_t count) : outs(o), n(o ? count : 0) {
-        for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
-    }
-    fhs_status keep(fhs_status st) {
-        kept = st == FHS_OK;
-        return st;
-    }
-    ~BatchOutT() {
-        if (kept) return;
-        for (size_t i = 0; i < n; ++i)
-            if (outs[i]) {
-                destroy_obj(outs[i]);
-                outs[i] = nullptr;
-            }
-    }
-};
-using BatchOut = BatchOutT<fhs_plaintext>;
 // Largest batch one launch takes (its item count is a grid dimension of the sampler, NTT, combine, decrypt
 // and CRT kernels, and its scratch is count x l x N words); bigger batches are processed in chunks of this
 // many items, with the same results as one call per item
@@ -1819,30 +1862,33 @@ extern "C" fhs_status fhs_ciphertext_import(fhs_context* c, const uint64_t* host
                                             fhs_ciphertext** out) {
     ENTER(c);
     if (!host || !out || ncomp < 2 || ncomp > 3) return fail(FHS_ERR_INVALID, "ciphertext_import: bad args");
-    fhs_ciphertext* ct;
-    fhs_status s = new_ct(c, ncomp, ci, scale, &ct);
-    if (s != FHS_OK) return s;
-    HIPCHK(hipMemcpyAsync(ct->d, host, ct_bytes(ct), hipMemcpyHostToDevice, c->st), "ciphertext_import");
+    NEW_CT(ct, ncomp, ci, scale);
+    HIPCHK(hipMemcpyAsync(ct->d, host, ct_bytes(ct.p), hipMemcpyHostToDevice, c->st), "ciphertext_import");
     HIPCHK(hipStreamSynchronize(c->st), "ciphertext_import");
-    *out = ct;
+    *out = ct.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_plaintext_import(fhs_context* c, const uint64_t* host, int ci, double scale,
                                            fhs_plaintext** out) {
     ENTER(c);
     if (!host || !out) return fail(FHS_ERR_INVALID, "plaintext_import: bad args");
-    fhs_plaintext* pt;
-    fhs_status s = new_pt(c, ci, scale, &pt);
-    if (s != FHS_OK) return s;
-    HIPCHK(hipMemcpyAsync(pt->d, host, pt_bytes(pt), hipMemcpyHostToDevice, c->st), "plaintext_import");
+    NEW_PT(pt, ci, scale);
+    HIPCHK(hipMemcpyAsync(pt->d, host, pt_bytes(pt.p), hipMemcpyHostToDevice, c->st), "plaintext_import");
     HIPCHK(hipStreamSynchronize(c->st), "plaintext_import");
-    *out = pt;
+    *out = pt.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_debug_fail_next_flushes(fhs_context* c, int count) {
     if (!c || count < 0) return fail(FHS_ERR_INVALID, "debug_fail_next_flushes: bad args");
     Guard g(c);
     c->debug_fail_flushes = count;
+    return FHS_OK;
+}
+extern "C" fhs_status fhs_debug_fail_alloc(fhs_context* c, int nth, int* was_armed) {
+    if (!c) return fail(FHS_ERR_INVALID, "debug_fail_alloc: null context");
+    Guard g(c);
+    if (was_armed) *was_armed = c->debug_fail_alloc >= 0;
+    c->debug_fail_alloc = nth < 0 ? -1 : nth;
     return FHS_OK;
 }
 extern "C" fhs_status fhs_ciphertext_device_ptr(const fhs_ciphertext* ct, void** dptr, uint64_t* bytes) {
@@ -1890,24 +1936,16 @@ static void fft_inplace(std::vector<std::complex<double>>& a, const std::vector<
 
 // values: count vectors of n complex (re,im) (or real when is_real); produces rounded coefficients
 
-// The encoder's periodic-row detection (fhs_kernels.hip k_enc_period): *tl = a scratch of one byte per row, or null
+// The encoder's periodic-row detection (fhs_kernels.hip k_enc_period): tl = a scratch of one byte per row, left empty
 // when no row can take the sparse form (fewer values than slots, a ring below 512, FHESPEAR_ENCODE_DENSE=1)
 static hipError_t enc_periods(fhs_context* c, const double* dvals, size_t cnt, size_t n, size_t stride, bool is_real,
-                              uint64_t** tl, size_t* tbytes) {
-    *tl = nullptr;
-    *tbytes = 0;
+                              DevTmp& tl) {
     static const bool dense = getenv("FHESPEAR_ENCODE_DENSE") != nullptr;
     const int smax = fhs::encode_sparse_max_log(c->logN);
     if (dense || smax < 1 || n != c->N / 2 || cnt == 0) return hipSuccess;
-    const size_t tb = (cnt + 7) & ~(size_t)7;
-    hipError_t e = dalloc(c, tl, tb);
-    if (e != hipSuccess) {
-        *tl = nullptr;
-        return e;
-    }
-    *tbytes = tb;
-    return fhs::launch_enc_period(dvals, (int)cnt, n, stride, is_real, smax, reinterpret_cast<unsigned char*>(*tl),
-                                  c->st);
+    hipError_t e = tl.alloc((cnt + 7) & ~(size_t)7);
+    if (e != hipSuccess) return e;
+    return fhs::launch_enc_period(dvals, (int)cnt, n, stride, is_real, smax, tl.as<unsigned char>(), c->st);
 }
 // Encode `cnt` value rows already in HBM (row v at dvals + v * stride doubles) into new plaintexts.
 // A batch of >= 32 rows (diagonal batches, not a client's few vectors) whose every row is periodic (tlog >= 1, read
@@ -1945,50 +1983,44 @@ static fhs_status encode_rows_dev(fhs_context* c, const double* dvals, size_t cn
     // encoder reduces into every limb and the NTT runs in place -- same limbs, A/B and test knob)
     static const bool unfused = getenv("FHESPEAR_ENCODE_UNFUSED") != nullptr;
     static const bool no_shadow = getenv("FHESPEAR_ENCODE_NO_SHADOW") != nullptr;
-    uint64_t *coef = nullptr, *tl = nullptr, *dptrs = nullptr;
-    const size_t cbytes = 8 * cnt * c->N;
-    size_t tbytes = 0;
-    hipError_t e = hipSuccess;
-    if (!unfused) e = dalloc(c, &coef, cbytes);
-    if (e == hipSuccess && rows_known) {
-        tbytes = (cnt + 7) & ~(size_t)7;
-        e = dalloc(c, &tl, tbytes);
-        if (e == hipSuccess) e = hipMemsetAsync(tl, ss_hint, cnt, c->st);
-    } else if (e == hipSuccess) {
-        e = enc_periods(c, dvals, cnt, n, stride, is_real, &tl, &tbytes);
+    DevTmp coef(c), tl(c);
+    if (!unfused) HIPCHK(coef.alloc(8 * cnt * c->N), "encode");
+    if (rows_known) {
+        HIPCHK(tl.alloc((cnt + 7) & ~(size_t)7), "encode");
+        HIPCHK(hipMemsetAsync(tl.p, ss_hint, cnt, c->st), "encode");
+    } else {
+        HIPCHK(enc_periods(c, dvals, cnt, n, stride, is_real, tl), "encode");
     }
     int ss = 0;
-    if (e == hipSuccess && tl && coef && !no_shadow && c->T.max_qbits <= 59 && cnt >= 32 && ss_hint >= 0) {
+    if (tl.p && coef.p && !no_shadow && c->T.max_qbits <= 59 && cnt >= 32) {
         ss = ss_hint;
-    } else if (e == hipSuccess && tl && coef && !no_shadow && c->T.max_qbits <= 59 && cnt >= 32) {
-        std::vector<unsigned char> th(cnt);
-        e = hipMemcpyAsync(th.data(), tl, cnt, hipMemcpyDeviceToHost, c->st);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-        if (e == hipSuccess) ss = *std::min_element(th.begin(), th.end());
+        if (ss_hint < 0) {
+            std::vector<unsigned char> th(cnt);
+            HIPCHK(hipMemcpyAsync(th.data(), tl.p, cnt, hipMemcpyDeviceToHost, c->st), "encode");
+            HIPCHK(hipStreamSynchronize(c->st), "encode");
+            ss = *std::min_element(th.begin(), th.end());
+        }
     }
-    fhs_status s0 = FHS_OK;
-    if (e == hipSuccess && ss > 0 && new_pts_compact(c, cnt, ci, scale, ss, outs) != FHS_OK) {
+    if (ss > 0 && new_pts_compact(c, cnt, ci, scale, ss, outs) != FHS_OK) {
         (void)hipGetLastError();   // no room for the compact block: a dense batch
         ss = 0;
     }
-    if (e == hipSuccess && ss == 0) s0 = new_pts(c, cnt, ci, scale, outs);
-    std::vector<uint64_t*> ptrs(2 * cnt, nullptr);
-    if (e == hipSuccess && s0 == FHS_OK) {
-        for (size_t v = 0; v < cnt; ++v) {
-            ptrs[v] = outs[v]->d;   // null for a compact batch
-            ptrs[cnt + v] = outs[v]->dc;
-        }
-        e = scratch(c, fhs_context::SCR_ENC_PTRS, 16 * cnt, &dptrs);
+    if (ss == 0) {
+        const fhs_status s0 = new_pts(c, cnt, ci, scale, outs);
+        if (s0 != FHS_OK) return s0;
     }
-    if (e == hipSuccess && s0 == FHS_OK) e = stage_h2d(c, dptrs, ptrs.data(), 16 * cnt);
-    if (e == hipSuccess && s0 == FHS_OK)
-        e = fhs::launch_encode(c->T, dvals, (int)cnt, n, stride, is_real, scale, reinterpret_cast<fhs::u64* const*>(dptrs),
-                               l, c->st, reinterpret_cast<double*>(coef), reinterpret_cast<const unsigned char*>(tl),
-                               ss ? reinterpret_cast<fhs::u64* const*>(dptrs + cnt) : nullptr, ss);
-    if (tl) dfree(c, tl, tbytes);
-    if (coef) dfree(c, coef, cbytes);
-    if (s0 != FHS_OK) return s0;
-    return e == hipSuccess ? FHS_OK : hip_fail(e, "encode");
+    std::vector<uint64_t*> ptrs(2 * cnt, nullptr);
+    for (size_t v = 0; v < cnt; ++v) {
+        ptrs[v] = outs[v]->d;   // null for a compact batch
+        ptrs[cnt + v] = outs[v]->dc;
+    }
+    uint64_t* dptrs = nullptr;
+    HIPCHK(scratch(c, fhs_context::SCR_ENC_PTRS, 16 * cnt, &dptrs), "encode");
+    HIPCHK(stage_h2d(c, dptrs, ptrs.data(), 16 * cnt), "encode");
+    HIPCHK(fhs::launch_encode(c->T, dvals, (int)cnt, n, stride, is_real, scale, reinterpret_cast<fhs::u64* const*>(dptrs),
+                              l, c->st, coef.as<double>(), tl.as<const unsigned char>(),
+                              ss ? reinterpret_cast<fhs::u64* const*>(dptrs + cnt) : nullptr, ss), "encode");
+    return FHS_OK;
 }
 static fhs_status encode_checks(fhs_context* c, size_t n, double scale, int ci) {
     if (n > c->N / 2) return fail(FHS_ERR_INVALID, "encode: more values than slots");
@@ -2010,17 +2042,13 @@ static fhs_status encode_many(fhs_context* c, const double* vals, size_t count, 
     HostTrace ht;
     for (size_t base = 0; base < count; base += chunk) {
         const size_t cnt = std::min(chunk, count - base);
-        uint64_t* dvals = nullptr;
-        HIPCHK(dalloc(c, &dvals, std::max<size_t>(8, 8 * cnt * stride)), "encode staging");
-        if (stride) {   // stage_h2d: through the pinned ring, no host wait, when it fits a segment (a client
-                        // batch of a few vectors), else a copy + synchronisation
-            hipError_t e = stage_h2d(c, dvals, vals + base * stride, 8 * cnt * stride);
-            if (e != hipSuccess) { dfree(c, dvals, 8 * cnt * stride); return hip_fail(e, "encode upload"); }
-        }
+        DevTmp dvals(c);
+        HIPCHK(dvals.alloc(8 * cnt * stride), "encode staging");
+        // stage_h2d: through the pinned ring, no host wait, when it fits a segment (a client batch of a few
+        // vectors), else a copy + synchronisation
+        if (stride) HIPCHK(stage_h2d(c, dvals.p, vals + base * stride, 8 * cnt * stride), "encode upload");
         ht.mark("encode: upload");
-        fhs_status s = encode_rows_dev(c, reinterpret_cast<const double*>(dvals), cnt, n, stride, is_real, scale, ci,
-                                       outs + base);
-        dfree(c, dvals, std::max<size_t>(8, 8 * cnt * stride));
+        fhs_status s = encode_rows_dev(c, dvals.as<const double>(), cnt, n, stride, is_real, scale, ci, outs + base);
         ht.mark("encode: objects+launch");
         if (ht.on) { hipStreamSynchronize(c->st); ht.mark("encode: gpu"); }
         if (s != FHS_OK) return s;
@@ -2050,15 +2078,16 @@ static fhs_status encode_diag_rows(fhs_context* c, const double* M1, const doubl
     const bool is_real = M2 == nullptr;
     BatchOut bo(out, (size_t)nrows);
     const size_t mb = 8ull * D * D;
-    uint64_t *dm = nullptr, *dvals = nullptr;
-    HIPCHK(dalloc(c, &dm, mb * (is_real ? 1 : 2)), "encode_diagonals matrix");
+    DevTmp dm(c);
+    HIPCHK(dm.alloc(mb * (is_real ? 1 : 2)), "encode_diagonals matrix");
     // D rows of D doubles, `ld` apart on the host, packed on the device (no host-side copy of a view)
-    hipError_t e = hipMemcpy2DAsync(dm, 8ull * D, M1, 8ull * ld, 8ull * D, D, hipMemcpyHostToDevice, c->st);
-    if (e == hipSuccess && !is_real)
-        e = hipMemcpy2DAsync((char*)dm + mb, 8ull * D, M2, 8ull * ld, 8ull * D, D, hipMemcpyHostToDevice, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);   // caller's buffers may be reused on return
-    const double* m1 = reinterpret_cast<const double*>(dm);
-    const double* m2 = is_real ? nullptr : reinterpret_cast<const double*>((char*)dm + mb);
+    const double* m1 = dm.as<const double>();
+    const double* m2 = is_real ? nullptr : m1 + (size_t)D * D;
+    HIPCHK(hipMemcpy2DAsync(dm.p, 8ull * D, M1, 8ull * ld, 8ull * D, D, hipMemcpyHostToDevice, c->st), "encode_diagonals");
+    if (!is_real)
+        HIPCHK(hipMemcpy2DAsync(dm.p + (size_t)D * D, 8ull * D, M2, 8ull * ld, 8ull * D, D, hipMemcpyHostToDevice, c->st),
+               "encode_diagonals");
+    HIPCHK(hipStreamSynchronize(c->st), "encode_diagonals");   // caller's buffers may be reused on return
     // the gathered rows repeat with period D (slot j reads column j mod D): periodic at t = n / D when that is a power
     // of two, so the compact factor is known without reading the detected periods back
     int ss_hint = 0;
@@ -2073,25 +2102,21 @@ static fhs_status encode_diag_rows(fhs_context* c, const double* M1, const doubl
     const bool known = ss_hint >= 1 && !full_rows;
     const size_t ng = known ? n >> ss_hint : n, gstride = is_real ? ng : 2 * ng;
     const size_t chunk = 2048;
-    for (size_t base = 0; e == hipSuccess && st == FHS_OK && base < (size_t)nrows; base += chunk) {
+    for (size_t base = 0; base < (size_t)nrows; base += chunk) {
         const size_t cnt = std::min(chunk, (size_t)nrows - base);
-        e = dalloc(c, &dvals, 8 * cnt * gstride);
-        if (e != hipSuccess) break;
-        for (size_t k = 0; e == hipSuccess && k < cnt;) {   // one gather per run of consecutive rows
+        DevTmp dvals(c);
+        HIPCHK(dvals.alloc(8 * cnt * gstride), "encode_diagonals");
+        for (size_t k = 0; k < cnt;) {   // one gather per run of consecutive rows
             size_t r = 1;
             while (k + r < cnt && rows[base + k + r] == rows[base + k] + (int)r) ++r;
-            e = fhs::launch_diag_gather(m1, m2, D, G, (int)ng, rows[base + k], (int)r, trans ? 1 : 0,
-                                        reinterpret_cast<double*>(dvals) + k * gstride, c->st);
+            HIPCHK(fhs::launch_diag_gather(m1, m2, D, G, (int)ng, rows[base + k], (int)r, trans ? 1 : 0,
+                                           dvals.as<double>() + k * gstride, c->st), "encode_diagonals");
             k += r;
         }
-        if (e == hipSuccess)
-            st = encode_rows_dev(c, reinterpret_cast<const double*>(dvals), cnt, n, gstride, is_real, scale, ci,
-                                 out + base, ss_hint, known);
-        dfree(c, dvals, 8 * cnt * gstride);
+        st = encode_rows_dev(c, dvals.as<const double>(), cnt, n, gstride, is_real, scale, ci, out + base, ss_hint, known);
+        if (st != FHS_OK) return st;
     }
-    dfree(c, dm, mb * (is_real ? 1 : 2));
-    if (e != hipSuccess) return hip_fail(e, "encode_diagonals");
-    return bo.keep(st);
+    return bo.keep(FHS_OK);
 }
 extern "C" fhs_status fhs_encode_diagonals_ex(fhs_context* c, const double* M1, const double* M2, int64_t ld, int trans,
                                               int D, int G, double scale, int ci, fhs_plaintext** out) {
@@ -2178,25 +2203,20 @@ extern "C" fhs_status fhs_encode_precise(fhs_context* c, const double* re_im, si
                         hi.data(), lo.data(), &overflow);
     for (auto& x : th) x.join();
     if (overflow.load()) return fail(FHS_ERR_INVALID, "encode_precise: |value x scale| >= 2^126 (or not finite)");
-    uint64_t* dbuf = nullptr;
-    HIPCHK(dalloc(c, &dbuf, 16 * count * N), "encode_precise staging");
-    hipError_t e = hipMemcpyAsync(dbuf, hi.data(), 8 * count * N, hipMemcpyHostToDevice, c->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbuf + count * N, lo.data(), 8 * count * N, hipMemcpyHostToDevice, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+    DevTmp dbuf(c);
+    HIPCHK(dbuf.alloc(16 * count * N), "encode_precise staging");
+    HIPCHK(hipMemcpyAsync(dbuf.p, hi.data(), 8 * count * N, hipMemcpyHostToDevice, c->st), "encode_precise");
+    HIPCHK(hipMemcpyAsync(dbuf.p + count * N, lo.data(), 8 * count * N, hipMemcpyHostToDevice, c->st), "encode_precise");
+    HIPCHK(hipStreamSynchronize(c->st), "encode_precise");
+    const fhs_status s = new_pts(c, count, ci, scale, outs);
+    if (s != FHS_OK) return s;
     std::vector<uint64_t*> ptrs(count);
-    if (e == hipSuccess) {
-        fhs_status s = new_pts(c, count, ci, scale, outs);
-        if (s != FHS_OK) { dfree(c, dbuf, 16 * count * N); return s; }
-        for (size_t v = 0; v < count; ++v) ptrs[v] = outs[v]->d;
-    }
+    for (size_t v = 0; v < count; ++v) ptrs[v] = outs[v]->d;
     uint64_t* dptrs = nullptr;
-    if (e == hipSuccess) e = scratch(c, fhs_context::SCR_ENC_PTRS, 8 * count, &dptrs);
-    if (e == hipSuccess) e = stage_h2d(c, dptrs, ptrs.data(), 8 * count);
-    if (e == hipSuccess)
-        e = fhs::launch_encode_int128(c->T, reinterpret_cast<const int64_t*>(dbuf), dbuf + count * N, (int)count,
-                                      reinterpret_cast<fhs::u64* const*>(dptrs), l, c->st);
-    dfree(c, dbuf, 16 * count * N);
-    if (e != hipSuccess) return hip_fail(e, "encode_precise");
+    HIPCHK(scratch(c, fhs_context::SCR_ENC_PTRS, 8 * count, &dptrs), "encode_precise");
+    HIPCHK(stage_h2d(c, dptrs, ptrs.data(), 8 * count), "encode_precise");
+    HIPCHK(fhs::launch_encode_int128(c->T, dbuf.as<const int64_t>(), dbuf.p + count * N, (int)count,
+                                     reinterpret_cast<fhs::u64* const*>(dptrs), l, c->st), "encode_precise");
     return bo.keep(FHS_OK);
 }
 
@@ -2406,63 +2426,42 @@ static fhs_status decode_coeffs_dev(fhs_context* c, const fhs_plaintext* pt, int
                                     bool* exact) {
     const size_t N = c->N, bytes = 8ull * lv * N;
     const int nx = lv - k;
+    constexpr size_t KW = sizeof(fhs::CrtConsts) / 8;
+    const std::vector<uint64_t>& tab = crt_tables(c, k, lv);   // [CrtConsts of k limbs][nx check tables]
     fhs::CrtConsts K;
-    crt_consts(c, k, K);
-    std::vector<uint64_t> vt((size_t)nx * fhs::kCrtVtabWords, 0);
-    for (int e = 0; e < nx; ++e) {
-        uint64_t* v = vt.data() + (size_t)e * fhs::kCrtVtabWords;
-        const uint64_t q = c->q[k + e];
-        const hu128 R = (~(hu128)0) / q;   // floor(2^128 / q) for odd q
-        v[0] = q;
-        v[1] = (uint64_t)R;
-        v[2] = (uint64_t)(R >> 64);
-        const uint64_t t64 = (uint64_t)((((hu128)1) << 64) % q);
-        uint64_t pw = 1 % q;
-        for (int w = 0; w < K.W; ++w) {
-            v[3 + w] = pw;
-            pw = h_mulmod(pw, t64, q);
-        }
-    }
-    const size_t extra_b = 8 * vt.size() + 8;   // vtab, then the mismatch flag
-    uint64_t *tmp = nullptr, *dbl = nullptr, *aux = nullptr;
-    HIPCHK(dalloc(c, &tmp, bytes), "decode");
-    hipError_t e = dalloc(c, &dbl, 8 * N);
-    if (e != hipSuccess) { dfree(c, tmp, bytes); return hip_fail(e, "decode"); }
-    e = dalloc(c, &aux, extra_b);
-    if (e != hipSuccess) { dfree(c, dbl, 8 * N); dfree(c, tmp, bytes); return hip_fail(e, "decode"); }
-    unsigned* flag = reinterpret_cast<unsigned*>(aux + vt.size());
+    std::memcpy(&K, tab.data(), sizeof(K));
+    const uint64_t* vt = tab.data() + KW;
+    const size_t vt_words = tab.size() - KW;
+    DevTmp tmp(c), dbl(c), aux(c);   // aux: the check tables, then the mismatch flag
+    HIPCHK(tmp.alloc(bytes), "decode");
+    HIPCHK(dbl.alloc(8 * N), "decode");
+    HIPCHK(aux.alloc(8 * vt_words + 8), "decode");
+    unsigned* flag = reinterpret_cast<unsigned*>(aux.p + vt_words);
     unsigned hflag = 0;
-    const uint64_t* pd = nullptr;
-    e = pt_dense(c, pt, &pd);
-    if (e == hipSuccess) e = hipMemcpyAsync(tmp, pd, bytes, hipMemcpyDeviceToDevice, c->st);
-    if (e == hipSuccess && nx > 0) e = stage_h2d(c, aux, vt.data(), 8 * vt.size());
-    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, 4, c->st);
-    if (e == hipSuccess) e = fhs::launch_ntt_inv(c->T, tmp, lv, lv, 1, 0, c->st);
-    if (e == hipSuccess)
-        e = fhs::launch_crt_compose(K, tmp, reinterpret_cast<double*>(dbl), (int)N, c->st, tmp + (size_t)k * N, nx, aux,
-                                    flag);
+    PT_DENSE(pd, pt, "decode");
+    HIPCHK(hipMemcpyAsync(tmp.p, pd, bytes, hipMemcpyDeviceToDevice, c->st), "decode");
+    if (nx > 0) HIPCHK(stage_h2d(c, aux.p, vt, 8 * vt_words), "decode");
+    HIPCHK(hipMemsetAsync(flag, 0, 4, c->st), "decode");
+    HIPCHK(fhs::launch_ntt_inv(c->T, tmp.p, lv, lv, 1, 0, c->st), "decode");
+    HIPCHK(fhs::launch_crt_compose(K, tmp.p, dbl.as<double>(), (int)N, c->st, tmp.p + (size_t)k * N, nx, aux.p, flag),
+           "decode");
     m.resize(N);
-    if (e == hipSuccess) e = hipMemcpyAsync(m.data(), dbl, 8 * N, hipMemcpyDeviceToHost, c->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, c->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-    dfree(c, aux, extra_b);
-    dfree(c, dbl, 8 * N);
-    dfree(c, tmp, bytes);
-    if (e != hipSuccess) return hip_fail(e, "decode");
+    HIPCHK(hipMemcpyAsync(m.data(), dbl.p, 8 * N, hipMemcpyDeviceToHost, c->st), "decode");
+    HIPCHK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, c->st), "decode");
+    HIPCHK(hipStreamSynchronize(c->st), "decode");
     *exact = hflag == 0;
     return FHS_OK;
 }
 static fhs_status decode_coeffs(fhs_context* c, const fhs_plaintext* pt, int k, std::vector<uint64_t>& host) {
     const size_t N = c->N, bytes = 8ull * k * N;
-    uint64_t* tmp = nullptr;
     PT_DENSE(pd, pt, "decode");
-    HIPCHK(dalloc(c, &tmp, bytes), "decode");
-    HIPCHK(hipMemcpyAsync(tmp, pd, bytes, hipMemcpyDeviceToDevice, c->st), "decode");
-    HIPCHK(fhs::launch_ntt_inv(c->T, tmp, k, k, 1, 0, c->st), "decode");
+    DevTmp tmp(c);
+    HIPCHK(tmp.alloc(bytes), "decode");
+    HIPCHK(hipMemcpyAsync(tmp.p, pd, bytes, hipMemcpyDeviceToDevice, c->st), "decode");
+    HIPCHK(fhs::launch_ntt_inv(c->T, tmp.p, k, k, 1, 0, c->st), "decode");
     host.resize((size_t)k * N);
-    HIPCHK(hipMemcpyAsync(host.data(), tmp, bytes, hipMemcpyDeviceToHost, c->st), "decode");
+    HIPCHK(hipMemcpyAsync(host.data(), tmp.p, bytes, hipMemcpyDeviceToHost, c->st), "decode");
     HIPCHK(hipStreamSynchronize(c->st), "decode");
-    dfree(c, tmp, bytes);
     return FHS_OK;
 }
 // centred coefficients of the first k limbs as doubles: composed on the GPU up to kCrtMaxL limbs (same
@@ -2564,14 +2563,14 @@ static fhs_status decode_many(fhs_context* c, const fhs_plaintext* const* pts, i
     const size_t aux_words = A0 + FW + slot_words;
     HostTrace ht;
     const size_t per_out = host_fft ? N : 2 * (size_t)nslots;   // doubles back per item
-    const size_t dbl_b = 8 * N * count, spec_b = 16 * n * count;
-    uint64_t *tmp = nullptr, *dbl = nullptr, *aux = nullptr, *spec = nullptr;
+    DevTmp tmp_h(c), dbl_h(c), aux_h(c), spec_h(c);
     double* rb = nullptr;
     hipError_t e = readback_buf(c, 8 * (FW + per_out * count), &rb);
-    if (e == hipSuccess && tmp_words) e = dalloc(c, &tmp, 8 * tmp_words);
-    if (e == hipSuccess) e = dalloc(c, &dbl, dbl_b);
-    if (e == hipSuccess) e = dalloc(c, &aux, 8 * aux_words);
-    if (e == hipSuccess && !host_fft) e = dalloc(c, &spec, spec_b);
+    if (e == hipSuccess && tmp_words) e = tmp_h.alloc(8 * tmp_words);
+    if (e == hipSuccess) e = dbl_h.alloc(8 * N * count);
+    if (e == hipSuccess) e = aux_h.alloc(8 * aux_words);
+    if (e == hipSuccess && !host_fft) e = spec_h.alloc(16 * n * count);
+    uint64_t *const tmp = tmp_h.p, *const dbl = dbl_h.p, *const aux = aux_h.p, *const spec = spec_h.p;
     const unsigned* hflag = reinterpret_cast<const unsigned*>(rb);
     double* rslots = rb + FW;
     const double* dscales = reinterpret_cast<const double*>(aux);
@@ -2641,10 +2640,9 @@ static fhs_status decode_many(fhs_context* c, const fhs_plaintext* const* pts, i
     for (int i = 0; st == FHS_OK && i < count; ++i) {
         if (fast[i] && hflag[i] == 0) continue;
         if (cts) {   // exact: all limbs, from the decrypted plaintext
-            fhs_plaintext* pt = nullptr;
-            st = fhs_decrypt(c, sk, cts[i], &pt);
-            if (st == FHS_OK) st = decode_compose(c, pt, pt->l, m);
-            if (pt) fhs_plaintext_destroy(pt);
+            Pt pt;
+            st = fhs_decrypt(c, sk, cts[i], &pt.p);
+            if (st == FHS_OK) st = decode_compose(c, pt.p, pt->l, m);
         } else {
             st = decode_compose(c, pts[i], pts[i]->l, m);   // exact: all limbs
         }
@@ -2671,10 +2669,6 @@ static fhs_status decode_many(fhs_context* c, const fhs_plaintext* const* pts, i
             std::memcpy(out, rslots + (size_t)i * per_out, 8 * per_out);
     }
     ht.mark("decode: slots");
-    if (spec) dfree(c, spec, spec_b);
-    if (aux) dfree(c, aux, 8 * aux_words);
-    if (dbl) dfree(c, dbl, dbl_b);
-    if (tmp) dfree(c, tmp, 8 * tmp_words);
     return st;
 }
 extern "C" fhs_status fhs_decode(fhs_context* c, const fhs_plaintext* pt, double* re_im) {
@@ -2715,20 +2709,17 @@ extern "C" fhs_status fhs_encrypt_symmetric(fhs_context* c, fhs_secret_key* sk, 
     ENTER(c);
     if (!sk || !pt || !out) return fail(FHS_ERR_INVALID, "encrypt: null argument");
     const uint64_t ctr = sk->ctr++;
-    fhs_ciphertext* ct;
-    fhs_status s = new_ct(c, 2, pt->ci, pt->scale, &ct);
-    if (s != FHS_OK) return s;
+    NEW_CT(ct, 2, pt->ci, pt->scale);
     const int l = pt->l;
     const size_t S = (size_t)l * c->N;
-    uint64_t* eb = nullptr;
-    HIPCHK(dalloc(c, &eb, 8 * S), "encrypt");
+    DevTmp eb(c);
+    HIPCHK(eb.alloc(8 * S), "encrypt");
     HIPCHK(fhs::launch_sample(c->T, fhs::SAMPLE_UNIFORM, sk->key, stream_id(ST_ENC_SYM, ctr, 0), ct->d + S, l, c->st), "encrypt");
-    HIPCHK(sample_small_ntt(c, fhs::SAMPLE_CBD, sk->key, stream_id(ST_ENC_SYM, ctr, 1), eb, l), "encrypt");
+    HIPCHK(sample_small_ntt(c, fhs::SAMPLE_CBD, sk->key, stream_id(ST_ENC_SYM, ctr, 1), eb.p, l), "encrypt");
     PT_DENSE(pd, pt, "encrypt");
-    HIPCHK(fhs::launch_encrypt_combine(c->T, 0, ct->d, ct->d + S, sk->s, nullptr, nullptr, eb, nullptr, pd, l, c->st),
+    HIPCHK(fhs::launch_encrypt_combine(c->T, 0, ct->d, ct->d + S, sk->s, nullptr, nullptr, eb.p, nullptr, pd, l, c->st),
            "encrypt");
-    dfree(c, eb, 8 * S);
-    *out = ct;
+    *out = ct.release();
     return FHS_OK;
 }
 // `count` symmetric encryptions at l limbs into new ciphertexts outs[i] (chain index ci, scale scales[i]):
@@ -2739,10 +2730,8 @@ static fhs_status encrypt_sym_core(fhs_context* c, fhs_secret_key* sk, int count
     BatchOutT<fhs_ciphertext> bo(outs, count);
     const size_t S = (size_t)l * c->N;
     for (int i = 0; i < count; ++i) {
-        fhs_ciphertext* ct;
-        fhs_status s = new_ct(c, 2, ci, scales[i], &ct);
+        fhs_status s = new_ct(c, 2, ci, scales[i], &outs[i]);
         if (s != FHS_OK) return s;
-        outs[i] = ct;
     }
     const uint64_t ctr0 = sk->ctr;
     sk->ctr += (uint64_t)count;
@@ -2756,21 +2745,16 @@ static fhs_status encrypt_sym_core(fhs_context* c, fhs_secret_key* sk, int count
             ptrs[count + i] = const_cast<uint64_t*>(pd);
         }
     }
-    uint64_t *eb = nullptr, *dptrs = nullptr, *small = nullptr;
-    const size_t small_b = ((size_t)c->N * count + 7) & ~(size_t)7;
-    HIPCHK(dalloc(c, &eb, 8 * S * count), "encrypt");
-    hipError_t e = dalloc(c, &dptrs, 16 * (size_t)count);
-    if (e == hipSuccess) e = dalloc(c, &small, small_b);
-    if (e == hipSuccess) e = stage_h2d(c, dptrs, ptrs.data(), 16 * (size_t)count);
-    if (e == hipSuccess)
-        e = fhs::launch_encrypt_sym_batch(c->T, sk->key, stream_id(ST_ENC_SYM, ctr0, 0), stream_id(ST_ENC_SYM, ctr0, 1),
-                                          step, reinterpret_cast<fhs::u64* const*>(dptrs), sk->s,
-                                          pts ? reinterpret_cast<const fhs::u64* const*>(dptrs + count) : nullptr,
-                                          count, l, reinterpret_cast<signed char*>(small), eb, c->st, coef);
-    if (small) dfree(c, small, small_b);
-    if (dptrs) dfree(c, dptrs, 16 * (size_t)count);
-    dfree(c, eb, 8 * S * count);
-    return bo.keep(e == hipSuccess ? FHS_OK : hip_fail(e, "encrypt"));
+    DevTmp eb(c), dptrs(c), small(c);
+    HIPCHK(eb.alloc(8 * S * count), "encrypt");
+    HIPCHK(dptrs.alloc(16 * (size_t)count), "encrypt");
+    HIPCHK(small.alloc(((size_t)c->N * count + 7) & ~(size_t)7), "encrypt");
+    HIPCHK(stage_h2d(c, dptrs.p, ptrs.data(), 16 * (size_t)count), "encrypt");
+    HIPCHK(fhs::launch_encrypt_sym_batch(c->T, sk->key, stream_id(ST_ENC_SYM, ctr0, 0), stream_id(ST_ENC_SYM, ctr0, 1),
+                                         step, dptrs.as<fhs::u64* const>(), sk->s,
+                                         pts ? reinterpret_cast<const fhs::u64* const*>(dptrs.p + count) : nullptr,
+                                         count, l, small.as<signed char>(), eb.p, c->st, coef), "encrypt");
+    return bo.keep(FHS_OK);
 }
 extern "C" fhs_status fhs_encrypt_symmetric_batch(fhs_context* c, fhs_secret_key* sk, const fhs_plaintext* const* pts,
                                                   int count, fhs_ciphertext** outs) {
@@ -2817,62 +2801,46 @@ extern "C" fhs_status fhs_encode_encrypt_symmetric_batch(fhs_context* c, fhs_sec
     if (count > (size_t)kMaxBatch) return fail(FHS_ERR_INVALID, "encode_encrypt: at most 4096 vectors per call");
     const size_t stride = is_real ? n : 2 * n, N = c->N;
     const int l = c->L0 + 1 - ci;
-    uint64_t *dvals = nullptr, *coef = nullptr;
-    const size_t vb = std::max<size_t>(8, 8 * count * stride), cb = 8 * count * N;
-    HIPCHK(dalloc(c, &dvals, vb), "encode_encrypt");
-    hipError_t e = dalloc(c, &coef, cb);
-    if (e == hipSuccess && stride) e = stage_h2d(c, dvals, values, 8 * count * stride);
-    uint64_t* tl = nullptr;   // periodic rows: the sparse encoding, as encode_*_batch gives them
-    size_t tbytes = 0;
-    if (e == hipSuccess)
-        e = enc_periods(c, reinterpret_cast<const double*>(dvals), count, n, stride, is_real != 0, &tl, &tbytes);
-    if (e == hipSuccess)
-        e = fhs::launch_encode_coef(c->T, reinterpret_cast<const double*>(dvals), (int)count, n, stride, is_real != 0,
-                                    scale, reinterpret_cast<double*>(coef), c->st, reinterpret_cast<const unsigned char*>(tl));
-    if (tl) dfree(c, tl, tbytes);
-    if (e == hipSuccess) {
-        std::vector<double> scales(count, scale);
-        st = encrypt_sym_core(c, sk, (int)count, l, ci, scales.data(), nullptr, reinterpret_cast<const double*>(coef),
-                              outs);
-    } else {
-        st = hip_fail(e, "encode_encrypt");
+    DevTmp dvals(c), coef(c);
+    HIPCHK(dvals.alloc(8 * count * stride), "encode_encrypt");
+    HIPCHK(coef.alloc(8 * count * N), "encode_encrypt");
+    if (stride) HIPCHK(stage_h2d(c, dvals.p, values, 8 * count * stride), "encode_encrypt");
+    {
+        DevTmp tl(c);   // periodic rows: the sparse encoding, as encode_*_batch gives them
+        HIPCHK(enc_periods(c, dvals.as<const double>(), count, n, stride, is_real != 0, tl), "encode_encrypt");
+        HIPCHK(fhs::launch_encode_coef(c->T, dvals.as<const double>(), (int)count, n, stride, is_real != 0, scale,
+                                       coef.as<double>(), c->st, tl.as<const unsigned char>()), "encode_encrypt");
     }
-    if (coef) dfree(c, coef, cb);
-    dfree(c, dvals, vb);
-    return st;
+    std::vector<double> scales(count, scale);
+    return encrypt_sym_core(c, sk, (int)count, l, ci, scales.data(), nullptr, coef.as<const double>(), outs);
 }
 extern "C" fhs_status fhs_encrypt_asymmetric(fhs_context* c, fhs_public_key* pk, const fhs_plaintext* pt,
                                              fhs_ciphertext** out) {
     ENTER(c);
     if (!pk || !pt || !out) return fail(FHS_ERR_INVALID, "encrypt: null argument");
     const uint64_t ctr = pk->ctr++;
-    fhs_ciphertext* ct;
-    fhs_status s = new_ct(c, 2, pt->ci, pt->scale, &ct);
-    if (s != FHS_OK) return s;
+    NEW_CT(ct, 2, pt->ci, pt->scale);
     const int l = pt->l;
     const size_t S = (size_t)l * c->N, SL = (size_t)c->L0 * c->N;
-    uint64_t* tmp = nullptr;
-    HIPCHK(dalloc(c, &tmp, 24 * S), "encrypt");
-    uint64_t *u = tmp, *e0 = tmp + S, *e1 = tmp + 2 * S;
+    DevTmp tmp(c);
+    HIPCHK(tmp.alloc(24 * S), "encrypt");
+    uint64_t *u = tmp.p, *e0 = tmp.p + S, *e1 = tmp.p + 2 * S;
     HIPCHK(sample_small_ntt(c, fhs::SAMPLE_TERNARY, pk->rng, stream_id(ST_ENC_ASYM, ctr, 0), u, l), "encrypt");
     HIPCHK(sample_small_ntt(c, fhs::SAMPLE_CBD, pk->rng, stream_id(ST_ENC_ASYM, ctr, 1), e0, l), "encrypt");
     HIPCHK(sample_small_ntt(c, fhs::SAMPLE_CBD, pk->rng, stream_id(ST_ENC_ASYM, ctr, 2), e1, l), "encrypt");
     PT_DENSE(pd, pt, "encrypt");
     HIPCHK(fhs::launch_encrypt_combine(c->T, 1, ct->d, ct->d + S, pk->pk, pk->pk + SL, u, e0, e1, pd, l, c->st),
            "encrypt");
-    dfree(c, tmp, 24 * S);
-    *out = ct;
+    *out = ct.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_decrypt(fhs_context* c, fhs_secret_key* sk, const fhs_ciphertext* ct, fhs_plaintext** out) {
     ENTER(c);
     if (!sk || !ct || !out) return fail(FHS_ERR_INVALID, "decrypt: null argument");
     LIVE(ct);
-    fhs_plaintext* pt;
-    fhs_status s = new_pt(c, ct->ci, ct->scale, &pt);
-    if (s != FHS_OK) return s;
+    NEW_PT(pt, ct->ci, ct->scale);
     HIPCHK(fhs::launch_decrypt(c->T, ct->d, ct->ncomp, sk->s, pt->d, ct->l, c->st), "decrypt");
-    *out = pt;
+    *out = pt.release();
     return FHS_OK;
 }
 
@@ -2891,12 +2859,10 @@ static fhs_status binop(fhs_context* c, int op, const fhs_ciphertext* a, const f
     if (s != FHS_OK) return s;
     if (a->ncomp != b->ncomp) return fail(FHS_ERR_INVALID, "ciphertext sizes differ");
     if (!scales_close(a->scale, b->scale)) return fail(FHS_ERR_SCALE, "scale mismatch");
-    fhs_ciphertext* r;
-    s = new_ct(c, a->ncomp, a->ci, a->scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, a->ncomp, a->ci, a->scale);
     const size_t cs = (size_t)a->l * c->N;
     HIPCHK(fhs::launch_eltwise(c->T, op, a->d, b->d, r->d, a->ncomp, a->l, cs, cs, c->st), "eltwise");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_add(fhs_context* c, const fhs_ciphertext* a, const fhs_ciphertext* b, fhs_ciphertext** out) {
@@ -2912,12 +2878,10 @@ extern "C" fhs_status fhs_negate(fhs_context* c, const fhs_ciphertext* a, fhs_ci
     ENTER(c);
     if (!a || !out) return fail(FHS_ERR_INVALID, "null argument");
     LIVE(a);
-    fhs_ciphertext* r;
-    fhs_status s = new_ct(c, a->ncomp, a->ci, a->scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, a->ncomp, a->ci, a->scale);
     const size_t cs = (size_t)a->l * c->N;
     HIPCHK(fhs::launch_eltwise(c->T, fhs::OP_NEG, a->d, nullptr, r->d, a->ncomp, a->l, cs, 0, c->st), "negate");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 static fhs_status plainop(fhs_context* c, int op, const fhs_ciphertext* a, const fhs_plaintext* p, fhs_ciphertext** out) {
@@ -2926,13 +2890,11 @@ static fhs_status plainop(fhs_context* c, int op, const fhs_ciphertext* a, const
     if (a->ci != p->ci) return fail(FHS_ERR_LEVEL, "ciphertext and plaintext are at different chain indices");
     const double sc = op == fhs::OP_MULP ? a->scale * p->scale : a->scale;
     if (op != fhs::OP_MULP && !scales_close(a->scale, p->scale)) return fail(FHS_ERR_SCALE, "scale mismatch");
-    fhs_ciphertext* r;
-    fhs_status s = new_ct(c, a->ncomp, a->ci, sc, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, a->ncomp, a->ci, sc);
     const size_t cs = (size_t)a->l * c->N;
     PT_DENSE(pd, p, "plain op");
     HIPCHK(fhs::launch_eltwise(c->T, op, a->d, pd, r->d, a->ncomp, a->l, cs, 0, c->st), "plain op");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_add_plain(fhs_context* c, const fhs_ciphertext* a, const fhs_plaintext* p, fhs_ciphertext** out) {
@@ -2956,11 +2918,9 @@ extern "C" fhs_status fhs_multiply(fhs_context* c, const fhs_ciphertext* a, cons
     fhs_status s = same_level(a, b);
     if (s != FHS_OK) return s;
     if (a->ncomp != 2 || b->ncomp != 2) return fail(FHS_ERR_INVALID, "multiply expects 2-component ciphertexts");
-    fhs_ciphertext* r;
-    s = new_ct(c, 3, a->ci, a->scale * b->scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, 3, a->ci, a->scale * b->scale);
     HIPCHK(fhs::launch_tensor(c->T, a->d, b->d, r->d, a->l, c->st), "multiply");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 
@@ -2986,14 +2946,12 @@ extern "C" fhs_status fhs_relinearize(fhs_context* c, const fhs_ciphertext* a, c
     if (!a || !rk || !out) return fail(FHS_ERR_INVALID, "null argument");
     LIVE(a);
     if (a->ncomp != 3) return fail(FHS_ERR_INVALID, "relinearize expects a 3-component ciphertext");
-    fhs_ciphertext* r;
-    fhs_status s = new_ct(c, 2, a->ci, a->scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, 2, a->ci, a->scale);
     const size_t S = (size_t)a->l * c->N;
     std::vector<KsItem> it{KsItem{a->d + 2 * S, a->d, a->d + S, rk->key, r->d, r->d + S, 1, 0, key_akey(c, rk->key)}};
-    s = run_keyswitch(c, it, a->l);
+    fhs_status s = run_keyswitch(c, it, a->l);
     if (s != FHS_OK) return s;
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 
@@ -3002,25 +2960,21 @@ extern "C" fhs_status fhs_rescale_to_next(fhs_context* c, const fhs_ciphertext* 
     if (!a || !out) return fail(FHS_ERR_INVALID, "null argument");
     LIVE(a);
     if (a->l < 2) return fail(FHS_ERR_LEVEL, "rescale_to_next: no level left (end of modulus switching chain)");
-    fhs_ciphertext* r;
-    fhs_status s = new_ct(c, a->ncomp, a->ci + 1, a->scale / (double)c->q[a->l - 1], &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, a->ncomp, a->ci + 1, a->scale / (double)c->q[a->l - 1]);
     uint64_t* scr = nullptr;
     HIPCHK(scratch(c, fhs_context::SCR_RESCALE, 8ull * a->ncomp * c->N, &scr), "rescale");
     HIPCHK(fhs::launch_rescale(c->T, a->d, r->d, scr, a->ncomp, a->l, c->st), "rescale");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 
 static fhs_status drop_ct(fhs_context* c, const fhs_ciphertext* a, int ci, fhs_ciphertext** out) {
     LIVE(a);
     if (ci < a->ci) return fail(FHS_ERR_LEVEL, "mod_switch_to: cannot switch to a higher level");
-    fhs_ciphertext* r;
-    fhs_status s = new_ct(c, a->ncomp, ci, a->scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, a->ncomp, ci, a->scale);
     const size_t row = 8ull * r->l * c->N, pitch = 8ull * a->l * c->N;
     HIPCHK(hipMemcpy2DAsync(r->d, row, a->d, pitch, row, a->ncomp, hipMemcpyDeviceToDevice, c->st), "mod_switch");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_mod_switch_to_next(fhs_context* c, const fhs_ciphertext* a, fhs_ciphertext** out) {
@@ -3037,12 +2991,10 @@ extern "C" fhs_status fhs_mod_switch_to(fhs_context* c, const fhs_ciphertext* a,
 }
 static fhs_status drop_pt(fhs_context* c, const fhs_plaintext* a, int ci, fhs_plaintext** out) {
     if (ci < a->ci || ci > c->L0) return fail(FHS_ERR_LEVEL, "mod_switch_to: bad target chain index");
-    fhs_plaintext* r;
-    fhs_status s = new_pt(c, ci, a->scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_PT(r, ci, a->scale);
     PT_DENSE(pd, a, "mod_switch");
-    HIPCHK(hipMemcpyAsync(r->d, pd, pt_bytes(r), hipMemcpyDeviceToDevice, c->st), "mod_switch");
-    *out = r;
+    HIPCHK(hipMemcpyAsync(r->d, pd, pt_bytes(r.p), hipMemcpyDeviceToDevice, c->st), "mod_switch");
+    *out = r.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_plain_mod_switch_to_next(fhs_context* c, const fhs_plaintext* a, fhs_plaintext** out) {
@@ -3069,7 +3021,7 @@ static fhs_status queue_rotation(fhs_context* c, const fhs_ciphertext* a, uint64
         fhs_status s = flush(c);
         if (s != FHS_OK) return s;
     }
-    fhs_ciphertext* r;
+    fhs_ciphertext* r;   // queued and handed out below: nothing fails in between
     fhs_status s = new_ct(c, 2, a->ci, a->scale, &r);
     if (s != FHS_OK) return s;
     const size_t S = (size_t)a->l * c->N;
@@ -3160,21 +3112,18 @@ static fhs_status bsgs_core(fhs_context* c, const fhs_ciphertext* const* baby, i
                             c->items_dev, c->stager, c->st, tm, ptl),
            "bsgs");
     ht.mark("launch bsgs");
-    fhs_ciphertext* r;
     if (!rescale) {
-        fhs_status s = new_ct(c, 2, ci, baby[0]->scale * pt_scale, &r);
-        if (s != FHS_OK) return s;
+        NEW_CT(r, 2, ci, baby[0]->scale * pt_scale);
         HIPCHK(hipMemcpyAsync(r->d, sum, 8 * 2 * S, hipMemcpyDeviceToDevice, c->st), "linear_transform");
-        *out = r;
+        *out = r.release();
         return FHS_OK;
     }
-    fhs_status s = new_ct(c, 2, ci + 1, baby[0]->scale * pt_scale / (double)c->q[l - 1], &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, 2, ci + 1, baby[0]->scale * pt_scale / (double)c->q[l - 1]);
     uint64_t* scr = nullptr;
     HIPCHK(scratch(c, fhs_context::SCR_RESCALE, 16ull * c->N, &scr), "bsgs rescale");
     HIPCHK(fhs::launch_rescale(c->T, sum, r->d, scr, 2, l, c->st, tm), "bsgs rescale");
     ht.mark("rescale+frees");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 
@@ -3245,20 +3194,14 @@ extern "C" fhs_status fhs_bsgs_inner_products(fhs_context* c, const fhs_cipherte
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_INNER, 8ull * std::max(B, 1) * 2 * S, &inner), "bsgs_inner_products");
     fhs_status cs = inner_products_core(c, baby, G, pts, B, inner);
     if (cs != FHS_OK) return cs;
-    std::vector<fhs_ciphertext*> made;
+    BatchOutT<fhs_ciphertext> bo(outs, (size_t)B);
     for (int g = 0; g < B; ++g) {
-        fhs_ciphertext* r;
-        fhs_status st = new_ct(c, 2, ci, baby[0]->scale * pts[0]->scale, &r);
-        if (st == FHS_OK && hipMemcpyAsync(r->d, inner + (size_t)g * 2 * S, 16 * S, hipMemcpyDeviceToDevice, c->st) != hipSuccess)
-            st = fail(FHS_ERR_HIP, "bsgs_inner_products: copy");
-        if (st != FHS_OK) {
-            for (fhs_ciphertext* m : made) fhs_ciphertext_destroy(m);
-            return st;
-        }
-        made.push_back(r);
-        outs[g] = r;
+        fhs_status st = new_ct(c, 2, ci, baby[0]->scale * pts[0]->scale, &outs[g]);
+        if (st != FHS_OK) return st;
+        HIPCHK(hipMemcpyAsync(outs[g]->d, inner + (size_t)g * 2 * S, 16 * S, hipMemcpyDeviceToDevice, c->st),
+               "bsgs_inner_products");
     }
-    return FHS_OK;
+    return bo.keep(FHS_OK);
 }
 
 // fhs_bsgs_inner_products into caller device memory (e.g. a torch buffer that a reduce-scatter then
@@ -3309,7 +3252,7 @@ extern "C" fhs_status fhs_dot_product_many(fhs_context* c, const fhs_ciphertext*
     if (rescale && l < 2) return fail(FHS_ERR_LEVEL, "rescale_to_next: no level left (end of modulus switching chain)");
     const size_t S = (size_t)l * c->N;
     const double sc = q[0]->scale * db[0]->scale;
-    // every allocation before the first launch: a failure leaves nothing behind and `outs` untouched
+    // every allocation before the first launch; the outputs are the caller's only on success (BatchOutT)
     uint64_t *t3 = nullptr, *relin = nullptr, *ws = nullptr, *scr = nullptr;
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_INNER, 8ull * C * 3 * S, &t3), "dot_product_many");
     if (rk && rescale) HIPCHK(scratch(c, fhs_context::SCR_BSGS_SUM, 8ull * C * 2 * S, &relin), "dot_product_many");
@@ -3318,23 +3261,19 @@ extern "C" fhs_status fhs_dot_product_many(fhs_context* c, const fhs_ciphertext*
     if (rk) HIPCHK(scratch(c, fhs_context::SCR_KS, wsb, &ws), "key-switch workspace");
     const int ocomp = rk ? 2 : 3;
     if (rescale) HIPCHK(scratch(c, fhs_context::SCR_RESCALE, 8ull * ocomp * C * c->N, &scr), "rescale");
-    std::vector<fhs_ciphertext*> made;
-    fhs_status s = new_cts(c, C, ocomp, rescale ? ci + 1 : ci, rescale ? sc / (double)c->q[l - 1] : sc, made);
+    BatchOutT<fhs_ciphertext> bo(outs, (size_t)C);
+    std::vector<fhs_ciphertext*> cts;
+    fhs_status s = new_cts(c, C, ocomp, rescale ? ci + 1 : ci, rescale ? sc / (double)c->q[l - 1] : sc, cts);
     if (s != FHS_OK) return s;
-    auto bail = [&](hipError_t e, const char* where) {
-        for (fhs_ciphertext* m : made) fhs_ciphertext_destroy(m);
-        return hip_fail(e, where);
-    };
+    std::copy(cts.begin(), cts.end(), outs);
     const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
-    hipError_t e = stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * (nq + nd));
-    if (e != hipSuccess) return bail(e, "dot_product_many");
+    HIPCHK(stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * (nq + nd)), "dot_product_many");
     const uint64_t* const* dq = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
     // the tensor sums land where the last stage reads them: the outputs' block itself when nothing follows
-    uint64_t* tdst = (!rk && !rescale) ? made[0]->d : t3;
-    e = fhs::launch_dot_tensor(c->T, dq, dq + J, J, C, l, tdst, c->st, tm);
-    if (e != hipSuccess) return bail(e, "dot_product_many");
+    uint64_t* tdst = (!rk && !rescale) ? outs[0]->d : t3;
+    HIPCHK(fhs::launch_dot_tensor(c->T, dq, dq + J, J, C, l, tdst, c->st, tm), "dot_product_many");
     if (rk) {
-        uint64_t* kdst = rescale ? relin : made[0]->d;   // [C][2][l][N]
+        uint64_t* kdst = rescale ? relin : outs[0]->d;   // [C][2][l][N]
         const uint64_t* akey = key_akey(c, rk->key);
         for (int c0 = 0; c0 < C; c0 += kDotKsBatch) {
             const int R = std::min(kDotKsBatch, C - c0);
@@ -3346,17 +3285,12 @@ extern "C" fhs_status fhs_dot_product_many(fhs_context* c, const fhs_ciphertext*
                 items[r] = KsItem{t + 2 * S, t, t + S, rk->key, o, o + S, 1, (uint64_t)r, akey};
                 uniq[r] = t + 2 * S;
             }
-            e = fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), R, l,
-                                      ws, wsb, c->items_dev, c->stager, c->st, tm);
-            if (e != hipSuccess) return bail(e, "key-switch");
+            HIPCHK(fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), R,
+                                         l, ws, wsb, c->items_dev, c->stager, c->st, tm), "key-switch");
         }
     }
-    if (rescale) {
-        e = fhs::launch_rescale(c->T, rk ? relin : t3, made[0]->d, scr, ocomp * C, l, c->st, tm);
-        if (e != hipSuccess) return bail(e, "rescale");
-    }
-    for (int k = 0; k < C; ++k) outs[k] = made[k];
-    return FHS_OK;
+    if (rescale) HIPCHK(fhs::launch_rescale(c->T, rk ? relin : t3, outs[0]->d, scr, ocomp * C, l, c->st, tm), "rescale");
+    return bo.keep(FHS_OK);
 }
 
 // Test hook: k_dot_tensor's per-coefficient schedule (dot3_term / dot3_finish, fhs_modarith.h: accumulate, fold,
@@ -3430,11 +3364,9 @@ static fhs_status giant_steps_core(fhs_context* c, Src src, int k, int ci, doubl
     HIPCHK(fhs::launch_bsgs(c->T, nullptr, nullptr, 1, B, B, l, keys.data(), akeys.data(), ge.data(), inner, sum, ws, wsb,
                             c->items_dev, c->stager, c->st, tm),
            "bsgs_giant_steps");
-    fhs_ciphertext* r;
-    fhs_status s = new_ct(c, 2, ci, scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, 2, ci, scale);
     HIPCHK(hipMemcpyAsync(r->d, sum, 16 * S, hipMemcpyDeviceToDevice, c->st), "bsgs_giant_steps");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_bsgs_giant_steps(fhs_context* c, const fhs_ciphertext* const* inners, int k,
@@ -3520,11 +3452,9 @@ extern "C" fhs_status fhs_multiply_const(fhs_context* c, const fhs_ciphertext* a
     fhs::ScalarConsts K;
     fhs_status s = scalar_consts(c, value * const_scale, a->l, K);
     if (s != FHS_OK) return s;
-    fhs_ciphertext* r;
-    s = new_ct(c, a->ncomp, a->ci, a->scale * const_scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, a->ncomp, a->ci, a->scale * const_scale);
     HIPCHK(fhs::launch_scalar(c->T, fhs::SCALAR_MUL, a->d, r->d, a->ncomp, a->l, K, c->st), "multiply_const");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_add_const(fhs_context* c, const fhs_ciphertext* a, double value, fhs_ciphertext** out) {
@@ -3534,11 +3464,9 @@ extern "C" fhs_status fhs_add_const(fhs_context* c, const fhs_ciphertext* a, dou
     fhs::ScalarConsts K;
     fhs_status s = scalar_consts(c, value * a->scale, a->l, K);
     if (s != FHS_OK) return s;
-    fhs_ciphertext* r;
-    s = new_ct(c, a->ncomp, a->ci, a->scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, a->ncomp, a->ci, a->scale);
     HIPCHK(fhs::launch_scalar(c->T, fhs::SCALAR_ADD, a->d, r->d, a->ncomp, a->l, K, c->st), "add_const");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_mod_raise(fhs_context* c, const fhs_ciphertext* a, fhs_ciphertext** out) {
@@ -3546,13 +3474,11 @@ extern "C" fhs_status fhs_mod_raise(fhs_context* c, const fhs_ciphertext* a, fhs
     if (!a || !out) return fail(FHS_ERR_INVALID, "null argument");
     LIVE(a);
     if (a->ncomp != 2) return fail(FHS_ERR_INVALID, "mod_raise expects a 2-component ciphertext");
-    fhs_ciphertext* r;
-    fhs_status s = new_ct(c, 2, 1, a->scale, &r);
-    if (s != FHS_OK) return s;
+    NEW_CT(r, 2, 1, a->scale);
     uint64_t* scr = nullptr;
     HIPCHK(scratch(c, fhs_context::SCR_RESCALE, 16ull * c->N, &scr), "mod_raise");
     HIPCHK(fhs::launch_mod_raise(c->T, a->d, a->l, r->d, scr, 2, c->st), "mod_raise");
-    *out = r;
+    *out = r.release();
     return FHS_OK;
 }
 
@@ -3561,32 +3487,6 @@ extern "C" fhs_status fhs_mod_raise(fhs_context* c, const fhs_ciphertext* a, fhs
 // per-call Python overhead dominated the bootstrap.  Every double expression mirrors the Python one
 // (same IEEE operations in the same order), so the limbs are identical.
 namespace {
-struct Ct {   // owning ciphertext handle
-    fhs_ciphertext* p = nullptr;
-    Ct() = default;
-    explicit Ct(fhs_ciphertext* x) : p(x) {}
-    Ct(const Ct&) = delete;
-    Ct& operator=(const Ct&) = delete;
-    Ct(Ct&& o) noexcept : p(o.p) { o.p = nullptr; }
-    Ct& operator=(Ct&& o) noexcept {
-        if (this != &o) {
-            reset();
-            p = o.p;
-            o.p = nullptr;
-        }
-        return *this;
-    }
-    ~Ct() { reset(); }
-    void reset() {
-        if (p) fhs_ciphertext_destroy(p);
-        p = nullptr;
-    }
-    fhs_ciphertext* release() {
-        fhs_ciphertext* x = p;
-        p = nullptr;
-        return x;
-    }
-};
 struct EmErr {
     fhs_status s;
 };
@@ -3796,14 +3696,12 @@ extern "C" fhs_status fhs_bsgs_from_cpu(fhs_context* c, const fhs_ciphertext* co
     for (int b = 0; b < G; ++b) LIVE(baby[b]);
     const int l = c->L0 + 1 - ci;
     const size_t bytes = 8ull * D * l * c->N;
-    uint64_t* dev = nullptr;
-    HIPCHK(dalloc(c, &dev, bytes), "bsgs_from_cpu staging");
-    HIPCHK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->st), "bsgs_from_cpu upload");
+    DevTmp dev(c);
+    HIPCHK(dev.alloc(bytes), "bsgs_from_cpu staging");
+    HIPCHK(hipMemcpyAsync(dev.p, host, bytes, hipMemcpyHostToDevice, c->st), "bsgs_from_cpu upload");
     std::vector<const uint64_t*> p(D);
-    for (int k = 0; k < D; ++k) p[k] = dev + (size_t)k * l * c->N;
-    fhs_status s = bsgs_core(c, baby, G, p.data(), D, B, ci, scale, gk, out);
-    dfree(c, dev, bytes);
-    return s;
+    for (int k = 0; k < D; ++k) p[k] = dev.p + (size_t)k * l * c->N;
+    return bsgs_core(c, baby, G, p.data(), D, B, ci, scale, gk, out);
 }
 
 // ============================================================================ measurement hooks
@@ -3909,16 +3807,10 @@ static fhs_status copy_to_device(fhs_context* c, const fhs_ciphertext* ct, void*
 static fhs_status from_device(fhs_context* c, const void* src, int ncomp, int ci, double scale, fhs_ciphertext** out,
                               bool sync) {
     if (!src || !out) return fail(FHS_ERR_INVALID, "null argument");
-    fhs_ciphertext* ct;
-    fhs_status s = new_ct(c, ncomp, ci, scale, &ct);
-    if (s != FHS_OK) return s;
-    hipError_t e = hipMemcpyAsync(ct->d, src, ct_bytes(ct), hipMemcpyDeviceToDevice, c->st);
-    if (e == hipSuccess && sync) e = hipStreamSynchronize(c->st);
-    if (e != hipSuccess) {
-        fhs_ciphertext_destroy(ct);
-        return hip_fail(e, "from_device");
-    }
-    *out = ct;
+    NEW_CT(ct, ncomp, ci, scale);
+    HIPCHK(hipMemcpyAsync(ct->d, src, ct_bytes(ct.p), hipMemcpyDeviceToDevice, c->st), "from_device");
+    if (sync) HIPCHK(hipStreamSynchronize(c->st), "from_device");
+    *out = ct.release();
     return FHS_OK;
 }
 extern "C" fhs_status fhs_ciphertext_copy_to_device(fhs_context* c, const fhs_ciphertext* ct, void* dst) {

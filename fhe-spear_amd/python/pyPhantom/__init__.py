@@ -189,6 +189,7 @@ _SIGS = {
     "fhs_context_stream": (C.c_int, [_vp, C.POINTER(_vp)]),
     "fhs_staging_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fhs_debug_fail_next_flushes": (C.c_int, [_vp, C.c_int]),
+    "fhs_debug_fail_alloc": (C.c_int, [_vp, C.c_int, _ip]),
 }
 # Fork-only symbols the reference probes with try/except AttributeError (bg:449-461, 382-391): if
 # the library lacks one (an older build, or FHESPEAR_DISABLE_SYMBOLS for tests), the Python names
@@ -1164,6 +1165,15 @@ def debug_fail_next_flushes(ctx, count=1):
     """Testing hook: the next `count` flushes of queued rotations fail as out of memory (their outputs are
     marked lost and the queue is dropped: fhs_debug_fail_next_flushes)."""
     _check(_lib.fhs_debug_fail_next_flushes(ctx._h, int(count)), "debug_fail_next_flushes")
+
+
+def debug_fail_alloc(ctx, nth):
+    """Testing hook: nth >= 0 makes the context's (nth+1)-th device allocation from now on fail once as out of
+    memory (cache hits count); nth < 0 disarms.  Returns whether an earlier arming was still pending
+    (fhs_debug_fail_alloc)."""
+    was = C.c_int()
+    _check(_lib.fhs_debug_fail_alloc(ctx._h, int(nth), C.byref(was)), "debug_fail_alloc")
+    return bool(was.value)
 
 
 def staging_stats(ctx):

@@ -57,6 +57,11 @@ fhs_status fhs_device_pci_bus_id(int device, char* buf, int len);
  * out of memory before launching, so the drop-the-queue path (queued outputs marked lost, later uses rejected)
  * can be exercised without exhausting HBM. */
 fhs_status fhs_debug_fail_next_flushes(fhs_context* ctx, int count);
+/* Testing hook (extension, replaces no pb symbol): nth >= 0 arms it -- the (nth+1)-th device allocation `ctx` makes
+ * from now on (cache hits included) fails once as out of memory, before the block cache is consulted and before any
+ * hipMalloc; nth < 0 disarms it.  *was_armed (may be NULL) receives whether an arming was still pending.  Launches
+ * nothing and touches no device state: every failure path can be walked without exhausting HBM. */
+fhs_status fhs_debug_fail_alloc(fhs_context* ctx, int nth, int* was_armed);
 
 /* ---- parameters (pb:78-98) ---- */
 /* pb:81 create_coeff_modulus: SEAL CoeffModulus::Create (largest primes = 1 mod 2N per size) */
