@@ -1,5 +1,7 @@
-// fhs_host.hip -- host side of libfhespear_hip.so: parameter tables, object lifetime, key
-// generation, CKKS encode/decode, and every extern "C" entry point of include/fhespear.h.
+// fhs_host.hip -- host side of libfhespear_hip.so: object lifetime, key generation, CKKS
+// encode/decode, and every extern "C" entry point of include/fhespear.h.  The parameter tables and
+// everything else that needs no device (number theory, argument validation, CRT constants) are
+// derived in fhs_tables.h; this file uploads them.
 //
 // Runtime model (MI355X-first):
 //  - one context = one device + one HIP stream; device blocks come from hipMalloc behind a bounded
@@ -35,10 +37,10 @@
 #include "../../include/fhespear.h"
 #include "fhs_kernels.h"
 #include "fhs_modarith.h"
+#include "fhs_tables.h"
 
 using fhs::DevTables;
 using fhs::KsItem;
-typedef unsigned __int128 hu128;
 
 // ============================================================================ errors
 static thread_local std::string g_err;
@@ -85,210 +87,15 @@ extern "C" fhs_status fhs_device_pci_bus_id(int device, char* buf, int len) {
     return FHS_OK;
 }
 
-// ============================================================================ host number theory
-static inline uint64_t h_mulmod(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)(((hu128)a * b) % q); }
-static uint64_t h_pow(uint64_t b, uint64_t e, uint64_t q) {
-    uint64_t r = 1 % q;
-    b %= q;
-    while (e) {
-        if (e & 1) r = h_mulmod(r, b, q);
-        b = h_mulmod(b, b, q);
-        e >>= 1;
-    }
-    return r;
-}
-static uint64_t h_inv(uint64_t a, uint64_t q) { return h_pow(a % q, q - 2, q); }
-static uint64_t h_shoup(uint64_t w, uint64_t q) { return (uint64_t)(((hu128)w << 64) / q); }
-
-// q = 2^b - d qualifies for pm_reduce128 (fhs_modarith.h) when its three folds provably take
-// every 128-bit input below 2q: B_{k+1} = (B_k >> b) d + 2^b - 1 from B_0 = 2^128 - 1, with the
-// fold-2 quotient < 2^64 and the fold-3 quotient < 2^32.  Returns the PrimeK.pm word or 0.
-static uint64_t pm_word(uint64_t q, int logN) {
-    int b = 64 - __builtin_clzll(q);
-    if (b < 40 || b > 62) return 0;
-    const uint64_t d = (1ull << b) - q;
-    if (d >= (1ull << 32)) return 0;
-    const hu128 lim = ((hu128)1 << b) - 1;
-    const hu128 B0 = ~(hu128)0;
-    const hu128 h1 = B0 >> b;                       // < 2^88: product with d may overflow -> check
-    if ((h1 >> 96) != 0) return 0;
-    const hu128 B1 = h1 * d + lim;                  // h1 < 2^96, d < 2^32 -> < 2^128
-    if (B1 < h1 * d) return 0;
-    const hu128 h2 = B1 >> b;
-    if ((h2 >> 64) != 0) return 0;
-    const hu128 B2 = h2 * d + lim;
-    const hu128 h3 = B2 >> b;
-    if ((h3 >> 32) != 0) return 0;
-    const hu128 B3 = h3 * d + lim;
-    if (B3 >= 2 * (hu128)q) return 0;
-    const bool lazy = (hu128)q * (uint64_t)(4 + 2 * logN) < ((hu128)1 << 64);   // fhs_ntt.h LAZY bound
-    return (d << 8) | (lazy ? 128u : 0u) | (uint64_t)b;
-}
-
-// A 59-bit prime q = 2^59 - d with d < 2^27: the precondition of convert3x_b59's bounds.
-static bool b59_prime(uint64_t q) { return q < (1ull << 59) && (1ull << 59) - q < (1ull << 27); }
-// Bit 40 of PrimeK.pm: the ModUp conversion may reduce its split-30 sums directly
-// (fhs_modarith.h acc3_reduce_pm): with ns <= P source limbs (< 2^60 each) and the v (Q mod m)
-// correction folded into L, every intermediate of that routine stays in its word and the result is
-// below 2q.  Checked here with exact bounds for this prime.
-static bool conv_pm_ok(uint64_t q, int ns) {
-    const int b = 64 - __builtin_clzll(q);
-    if (b < 40 || b > 60 || ns < 1 || ns > 7) return false;
-    const hu128 d = ((hu128)1 << b) - q;
-    const hu128 p30 = ((hu128)1 << 30) - 1, M64 = ~(hu128)0 >> 64;   // 2^64 - 1
-    const hu128 Lmax = (hu128)ns * p30 * p30 + (hu128)ns * (q - 1);
-    const hu128 Mmax = (hu128)2 * ns * p30 * p30, Hmax = (hu128)ns * p30 * p30;
-    const int sh = b - 30;
-    const hu128 Amax = Lmax + ((((hu128)1 << sh) - 1) << 30);
-    const hu128 Bmax = (Mmax >> sh) + (Hmax << (60 - b));
-    if (Lmax > M64 || Mmax > M64 || Amax > M64 || Bmax > M64) return false;
-    if ((Bmax >> 64) != 0 || d >= ((hu128)1 << 32)) return false;
-    const hu128 Smax = Amax + Bmax * d;   // < 2^96
-    const hu128 Sh = Smax >> b;
-    if (Sh >= ((hu128)1 << 32)) return false;
-    const hu128 rmax = (((hu128)1 << b) - 1) + Sh * d;
-    return rmax < 2 * (hu128)q;
-}
-// X form of the centred extension for full 3-limb digits (fhs_modarith.h centered_x_pack /
-// convert3x_value, fhs_kernels.hip k_centered_x): per digit j (primes 3j..3j+2, j < dnum with 3j + 3 <=
-// L0) the exact Q_S / q_u, the rounding thresholds ((2k - 1) Q_S + 1) / 2 and 2^179 - v Q_S (192-bit
-// words, little-endian) into xd[j][32]; per prime m the base-2^60 weights 2^60, 2^120 mod m (split-30
-// packed) and -2^179 mod m into xt[i][4].  |X| < Q_S / 2 < 2^179 (three primes below 2^60; < 2^176 for the
-// 59-bit chain), so U = X + 2^179 lies in (0, 2^180): exactly three 60-bit words.
-static void modup_xform_tables(const uint64_t* primes, int K, int L0, int dnum, uint64_t* xd, uint64_t* xt) {
-    auto mul192 = [](const uint64_t a[3], uint64_t m, uint64_t r[3]) {   // r = a m mod 2^192
-        hu128 cy = 0;
-        for (int w = 0; w < 3; ++w) {
-            const hu128 t = (hu128)a[w] * m + cy;
-            r[w] = (uint64_t)t;
-            cy = t >> 64;
-        }
-    };
-    for (int j = 0; j < dnum && 3 * j + 3 <= L0; ++j) {
-        const uint64_t* q3 = &primes[3 * j];
-        uint64_t* d = &xd[(size_t)j * 32];
-        for (int u = 0; u < 3; ++u) {
-            const hu128 h = (hu128)q3[(u + 1) % 3] * q3[(u + 2) % 3];
-            d[2 * u] = (uint64_t)h;
-            d[2 * u + 1] = (uint64_t)(h >> 64);
-        }
-        const uint64_t one[3] = {1, 0, 0};
-        uint64_t Q[3], t[3];
-        mul192(one, q3[0], t);
-        mul192(t, q3[1], Q);
-        mul192(Q, q3[2], t);
-        std::copy(t, t + 3, Q);
-        for (int k = 1; k <= 3; ++k) {   // ((2k - 1) Q + 1) / 2: (2k - 1) Q is odd, so + 1 is carry-free
-            uint64_t m[3];
-            mul192(Q, (uint64_t)(2 * k - 1), m);
-            m[0] += 1;
-            uint64_t* th = d + 6 + 3 * (k - 1);
-            th[0] = (m[0] >> 1) | (m[1] << 63);
-            th[1] = (m[1] >> 1) | (m[2] << 63);
-            th[2] = m[2] >> 1;
-        }
-        for (int v = 0; v <= 3; ++v) {   // 2^179 - v Q
-            uint64_t m[3];
-            mul192(Q, (uint64_t)v, m);
-            uint64_t* c = d + 15 + 3 * v;
-            const uint64_t top[3] = {0, 0, 1ull << (179 - 128)};
-            uint64_t br = 0;
-            for (int w = 0; w < 3; ++w) {
-                const hu128 s = (hu128)top[w] - m[w] - br;
-                c[w] = (uint64_t)s;
-                br = (uint64_t)(s >> 64) ? 1 : 0;
-            }
-        }
-    }
-    for (int i = 0; i < K; ++i) {
-        const uint64_t m = primes[i];
-        uint64_t p60 = 1 % m;
-        for (int e = 0; e < 60; ++e) p60 = h_mulmod(p60, 2, m);
-        const uint64_t p120 = h_mulmod(p60, p60, m);
-        uint64_t p179 = 1 % m;
-        for (int e = 0; e < 179; ++e) p179 = h_mulmod(p179, 2, m);
-        xt[(size_t)i * 4 + 0] = p60;   // convert3x_value takes it as one 32-bit word (< 2^30 checked by the caller)
-        xt[(size_t)i * 4 + 1] = pack30(p120);
-        xt[(size_t)i * 4 + 2] = p179 ? m - p179 : 0;
-    }
-}
-static bool h_is_prime(uint64_t n) {
-    if (n < 2) return false;
-    const uint64_t bases[] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37};
-    for (uint64_t p : bases) {
-        if (n == p) return true;
-        if (n % p == 0) return false;
-    }
-    uint64_t d = n - 1;
-    int s = 0;
-    while (!(d & 1)) { d >>= 1; ++s; }
-    for (uint64_t a : bases) {
-        uint64_t x = h_pow(a, d, n);
-        if (x == 1 || x == n - 1) continue;
-        bool comp = true;
-        for (int r = 1; r < s && comp; ++r) {
-            x = h_mulmod(x, x, n);
-            if (x == n - 1) comp = false;
-        }
-        if (comp) return false;
-    }
-    return true;
-}
-static uint32_t h_bitrev(uint32_t x, int bits) {
-    uint32_t r = 0;
-    for (int i = 0; i < bits; ++i) { r = (r << 1) | (x & 1); x >>= 1; }
-    return r;
-}
-// minimal primitive 2N-th root of unity mod q (SEAL / Phantom convention)
-static uint64_t h_min_root(uint64_t q, uint64_t N) {
-    const uint64_t cof = (q - 1) / (2 * N);
-    uint64_t g = 0;
-    for (uint64_t c = 2;; ++c) {
-        g = h_pow(c, cof, q);
-        if (h_pow(g, N, q) == q - 1) break;
-    }
-    const uint64_t g2 = h_mulmod(g, g, q);
-    uint64_t best = g, cur = g;
-    for (uint64_t k = 1; k < N; ++k) {
-        cur = h_mulmod(cur, g2, q);
-        if (cur < best) best = cur;
-    }
-    return best;
-}
-
+// ============================================================================ pure helpers (fhs_tables.h)
 extern "C" fhs_status fhs_create_coeff_modulus(uint64_t N, const int* bits, int n, uint64_t* out) {
     if (!bits || !out || n <= 0 || N < 2 || (N & (N - 1))) return fail(FHS_ERR_INVALID, "create_coeff_modulus: bad args");
-    const uint64_t fac = 2 * N;
-    std::map<int, std::vector<uint64_t>> pool;
-    std::map<int, int> need, used;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i)
         if (bits[i] < 2 || bits[i] > 61) return fail(FHS_ERR_INVALID, "create_coeff_modulus: bit size must be in [2, 61]");
-        need[bits[i]]++;
-    }
-    for (auto& kv : need) {
-        const int b = kv.first;
-        uint64_t v = ((uint64_t)1 << b) - fac + 1;
-        const uint64_t lo = (uint64_t)1 << (b - 1);
-        while ((int)pool[b].size() < kv.second && v > lo) {
-            if (h_is_prime(v)) pool[b].push_back(v);
-            v -= fac;
-        }
-        if ((int)pool[b].size() < kv.second) return fail(FHS_ERR_INVALID, "create_coeff_modulus: not enough primes");
-    }
-    for (int i = 0; i < n; ++i) out[i] = pool[bits[i]][used[bits[i]]++];
+    if (!coeff_modulus_search(N, bits, n, out)) return fail(FHS_ERR_INVALID, "create_coeff_modulus: not enough primes");
     return FHS_OK;
 }
-
-extern "C" uint64_t fhs_galois_elt_from_step(int step, uint64_t N) {
-    const uint64_t m = 2 * N;
-    if (step == 0) return m - 1;
-    const uint64_t slots = N / 2;
-    uint64_t s = step > 0 ? (uint64_t)step : slots - (uint64_t)(-(int64_t)step);
-    s %= slots;
-    uint64_t e = 1;
-    for (uint64_t i = 0; i < s; ++i) e = (e * 5) & (m - 1);
-    return e;
-}
+extern "C" uint64_t fhs_galois_elt_from_step(int step, uint64_t N) { return galois_elt_from_step(step, N); }
 
 // ============================================================================ objects
 struct PendingRot {
@@ -1054,40 +861,41 @@ static fhs_status live_ct(const fhs_ciphertext* a) {
     } while (0)
 
 // ============================================================================ context
+static void ctx_free(fhs_context* c);
+// One table into a device block of its own, the context's (c->tables) from the moment it exists
+static hipError_t upload_table(fhs_context* c, const void* src, size_t bytes, const void** dst) {
+    void* d = nullptr;
+    const hipError_t e = hipMalloc(&d, bytes);
+    if (e != hipSuccess) return e;
+    c->tables.push_back(d);
+    *dst = d;
+    return hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+}
+// Validate, select the device, derive every table on the host (fhs_tables.h), then the device side: nothing
+// touches the HIP runtime before the arguments have passed, and from its first resource on the half-built
+// context is released by ctx_free on every way out but the last.
 extern "C" fhs_status fhs_context_create(uint64_t N, const uint64_t* primes, int nprimes, int special,
                                          const uint64_t* galois_elts, int n_elts, int device, fhs_context** out) {
-    if (!primes || !out) return fail(FHS_ERR_INVALID, "context_create: null argument");
+    if (!out) return fail(FHS_ERR_INVALID, "context_create: null argument");
+    if (const char* bad = context_params_error(N, primes, nprimes, special, galois_elts, n_elts))
+        return fail(FHS_ERR_INVALID, bad);
     segv_trace_install();
-    if (N < 256 || N > 32768 || (N & (N - 1)))
-        return fail(FHS_ERR_INVALID, "context_create: poly_modulus_degree must be a power of two in [256, 32768]");
-    if (special < 1 || special >= nprimes) return fail(FHS_ERR_INVALID, "context_create: bad special modulus size");
-    const int L0 = nprimes - special;
-    if (L0 % special != 0)
-        return fail(FHS_ERR_INVALID,
-                    "context_create: data primes (L0) must be a multiple of special_modulus_size (README.md:59)");
-    if (special > 8) return fail(FHS_ERR_INVALID, "context_create: special_modulus_size > 8 unsupported");
-    for (int i = 0; i < nprimes; ++i) {
-        if (primes[i] >= (1ull << 60) || (primes[i] - 1) % (2 * N) != 0 || !h_is_prime(primes[i]))
-            return fail(FHS_ERR_INVALID, "context_create: every modulus must be a prime < 2^60 (SEAL's 60-bit "
-                                         "limit; Acc3 in fhs_modarith.h relies on it), = 1 mod 2N");
-        for (int j = 0; j < i; ++j)
-            if (primes[j] == primes[i]) return fail(FHS_ERR_INVALID, "context_create: duplicate modulus");
-    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(FHS_ERR_NODEVICE, "no HIP device: libfhespear_hip needs an MI355X (gfx950)");
     if (device < 0 || device >= ndev) return fail(FHS_ERR_INVALID, "context_create: bad device index");
     HIPCHK(hipSetDevice(device), "hipSetDevice");
 
-    auto c = std::make_unique<fhs_context>();
+    HostTables H;
+    if (const char* bad = build_host_tables(N, primes, nprimes, special, H)) return fail(FHS_ERR_INVALID, bad);
+
+    std::unique_ptr<fhs_context, void (*)(fhs_context*)> c(new fhs_context, ctx_free);
     c->device = device;
-    c->N = N;
-    while ((1ull << c->logN) < N) c->logN++;
-    c->K = nprimes;
-    c->P = special;
-    c->L0 = L0;
-    c->dnum = (L0 + special - 1) / special;
+    c->N = N; c->logN = H.logN; c->K = H.K; c->P = H.P; c->L0 = H.L0; c->dnum = H.dnum;
     c->q.assign(primes, primes + nprimes);
+    c->elts = galois_elts && n_elts > 0 ? std::vector<uint64_t>(galois_elts, galois_elts + n_elts) : default_galois_elts(N);
+    c->fft_w = std::move(H.fft_w);
+    c->slot_index = std::move(H.slot_index);
     HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking), "hipStreamCreate");
     {
         static std::once_flag exit_once;
@@ -1100,254 +908,22 @@ extern "C" fhs_status fhs_context_create(uint64_t N, const uint64_t* primes, int
         c->seal_corr_cap = total_b ? total_b / 16 : (size_t)16 << 30;
         if (const char* e = getenv("FHESPEAR_SEAL_CORR_BYTES")) c->seal_corr_cap = strtoull(e, nullptr, 10);
     }
-    if (galois_elts && n_elts > 0) {
-        c->elts.assign(galois_elts, galois_elts + n_elts);
-    } else {   // default: +-2^k steps and conjugation (SEAL/Phantom create_galois_keys default)
-        std::set<uint64_t> s;
-        for (uint64_t k = 1; k < N / 2; k <<= 1) {
-            s.insert(fhs_galois_elt_from_step((int)k, N));
-            s.insert(fhs_galois_elt_from_step(-(int)k, N));
-        }
-        s.insert(2 * N - 1);
-        c->elts.assign(s.begin(), s.end());
-    }
-    for (uint64_t e : c->elts)
-        if ((e & 1) == 0 || e >= 2 * N) return fail(FHS_ERR_INVALID, "context_create: invalid galois element");
-
-    const int K = nprimes, P = special, dnum = c->dnum;
-    // ---- per-prime constants and twiddles
-    std::vector<PrimeK> pk(K);
-    std::vector<uint64_t> twf((size_t)K * N * 2), twi((size_t)K * N * 2);
-    for (int i = 0; i < K; ++i) {
-        const uint64_t q = primes[i];
-        const hu128 r = (~(hu128)0) / q;
-        const uint64_t psi = h_min_root(q, N), ipsi = h_inv(psi, q);
-        uint64_t pw = 1, ipw = 1;
-        for (uint64_t k = 0; k < N; ++k) {
-            const uint32_t rv = h_bitrev((uint32_t)k, c->logN);
-            twf[((size_t)i * N + rv) * 2] = pw;
-            twi[((size_t)i * N + rv) * 2] = ipw;
-            pw = h_mulmod(pw, psi, q);
-            ipw = h_mulmod(ipw, ipsi, q);
-        }
-        for (uint64_t k = 0; k < N; ++k) {
-            twf[((size_t)i * N + k) * 2 + 1] = h_shoup(twf[((size_t)i * N + k) * 2], q);
-            twi[((size_t)i * N + k) * 2 + 1] = h_shoup(twi[((size_t)i * N + k) * 2], q);
-        }
-        const uint64_t ninv = h_inv(N % q, q);
-        const uint64_t w1n = h_mulmod(twi[((size_t)i * N + 1) * 2], ninv, q);
-        pk[i] = PrimeK{q, (uint64_t)r, (uint64_t)(r >> 64), ninv, h_shoup(ninv, q), w1n, h_shoup(w1n, q), pm_word(q, c->logN) | (pm_word(q, c->logN) && conv_pm_ok(q, special) ? (1ull << 40) : 0ull)};
-    }
-    // ---- ModUp tables per level l: digit j covers [jP, min(jP+P, l))
-    std::vector<uint64_t> mu_intt((size_t)(L0 + 1) * L0 * 4, 0), mu_hat((size_t)(L0 + 1) * dnum * P * K, 0);
-    for (int l = 1; l <= L0; ++l) {
-        const int dn = (l + P - 1) / P;
-        for (int j = 0; j < dn; ++j) {
-            const int s0 = j * P, s1 = std::min(s0 + P, l), ns = s1 - s0;
-            for (int u = 0; u < ns; ++u) {
-                const int i = s0 + u;
-                const uint64_t q = primes[i];
-                uint64_t hat = 1;
-                for (int v = 0; v < ns; ++v)
-                    if (v != u) hat = h_mulmod(hat, primes[s0 + v] % q, q);
-                const uint64_t ih = h_inv(hat, q);
-                const uint64_t a = h_mulmod(pk[i].ninv, ih, q), b = h_mulmod(pk[i].w1ninv, ih, q);
-                uint64_t* d = &mu_intt[((size_t)l * L0 + i) * 4];
-                d[0] = a; d[1] = h_shoup(a, q); d[2] = b; d[3] = h_shoup(b, q);
-                for (int t = 0; t < K; ++t) {
-                    const uint64_t m = primes[t];
-                    uint64_t h = 1;
-                    for (int v = 0; v < ns; ++v)
-                        if (v != u) h = h_mulmod(h, primes[s0 + v] % m, m);
-                    mu_hat[(((size_t)l * dnum + j) * P + u) * K + t] = h;
-                }
-            }
-        }
-    }
-    // ---- centred-extension tables: floor(2^128/q_u) per digit source, Q_S and ns Q_S mod every prime
-    std::vector<uint64_t> mu_R((size_t)(L0 + 1) * dnum * P * 2, 0), mu_Q((size_t)(L0 + 1) * dnum * K * 2, 0);
-    for (int l = 1; l <= L0; ++l) {
-        const int dn = (l + P - 1) / P;
-        for (int j = 0; j < dn; ++j) {
-            const int s0 = j * P, s1 = std::min(s0 + P, l), ns = s1 - s0;
-            for (int u = 0; u < ns; ++u) {
-                const hu128 R = (~(hu128)0) / primes[s0 + u];
-                mu_R[(((size_t)l * dnum + j) * P + u) * 2 + 0] = (uint64_t)R;
-                mu_R[(((size_t)l * dnum + j) * P + u) * 2 + 1] = (uint64_t)(R >> 64);
-            }
-            for (int t = 0; t < K; ++t) {
-                const uint64_t m = primes[t];
-                uint64_t Qm = 1;
-                for (int u = 0; u < ns; ++u) Qm = h_mulmod(Qm, primes[s0 + u] % m, m);
-                mu_Q[(((size_t)l * dnum + j) * K + t) * 2 + 0] = Qm;
-                mu_Q[(((size_t)l * dnum + j) * K + t) * 2 + 1] = h_mulmod(Qm, (uint64_t)ns, m);
-            }
-        }
-    }
-    std::vector<uint64_t> mu_xd((size_t)dnum * 32, 0), mu_xt((size_t)K * 4, 0);
-    if (P == 3) modup_xform_tables(primes, K, L0, dnum, mu_xd.data(), mu_xt.data());
-    // ---- ModDown tables
-    // X form of the special digit (fhs_kernels.hip k_special_x): Y = sum_k y_k (P/p_k) < 3P stored as
-    // base-2^60 words -- no centring (thresholds all ones), no offset (C_0 = 0); needs 3P < 2^180, so
-    // special primes below 2^59
-    std::vector<uint64_t> md_xd(32, 0);
-    bool md_x_ok = P == 3;
-    for (int k = 0; k < P && md_x_ok; ++k) md_x_ok = primes[L0 + k] < (1ull << 59);
-    if (md_x_ok) {
-        for (int u = 0; u < 3; ++u) {
-            const hu128 h = (hu128)primes[L0 + (u + 1) % 3] * primes[L0 + (u + 2) % 3];
-            md_xd[2 * u] = (uint64_t)h;
-            md_xd[2 * u + 1] = (uint64_t)(h >> 64);
-        }
-        for (int w = 6; w < 15; ++w) md_xd[w] = ~0ull;
-    }
-    std::vector<uint64_t> md_intt((size_t)P * 4), md_hat((size_t)P * L0), md_pinv((size_t)4 * L0);
-    for (int k = 0; k < P; ++k) {
-        const int pi = L0 + k;
-        const uint64_t p = primes[pi];
-        uint64_t hat = 1;
-        for (int v = 0; v < P; ++v)
-            if (v != k) hat = h_mulmod(hat, primes[L0 + v] % p, p);
-        const uint64_t ih = h_inv(hat, p);
-        const uint64_t a = h_mulmod(pk[pi].ninv, ih, p), b = h_mulmod(pk[pi].w1ninv, ih, p);
-        md_intt[k * 4 + 0] = a; md_intt[k * 4 + 1] = h_shoup(a, p);
-        md_intt[k * 4 + 2] = b; md_intt[k * 4 + 3] = h_shoup(b, p);
-        for (int i = 0; i < L0; ++i) {
-            const uint64_t q = primes[i];
-            uint64_t h = 1;
-            for (int v = 0; v < P; ++v)
-                if (v != k) h = h_mulmod(h, primes[L0 + v] % q, q);
-            md_hat[(size_t)k * L0 + i] = h;
-        }
-    }
-    for (int i = 0; i < L0; ++i) {
-        const uint64_t q = primes[i];
-        uint64_t pm = 1;
-        for (int k = 0; k < P; ++k) pm = h_mulmod(pm, primes[L0 + k] % q, q);
-        const uint64_t pinv = h_inv(pm, q);
-        md_pinv[2 * i] = pinv;
-        md_pinv[2 * i + 1] = h_shoup(pinv, q);
-        md_pinv[2 * L0 + i] = pm;
-        md_pinv[3 * L0 + i] = P == 1 ? (primes[L0] >> 1) % q : 0;   // SEAL ModDown rounding (P = 1)
-    }
-    // ---- rescale tables: level l (limbs) drops q_{l-1}
-    std::vector<uint64_t> rs((size_t)(L0 + 1) * L0 * 4, 0);
-    for (int l = 2; l <= L0; ++l) {
-        const uint64_t ql = primes[l - 1], half = ql >> 1;
-        for (int i = 0; i < l - 1; ++i) {
-            const uint64_t q = primes[i];
-            const uint64_t inv = h_inv(ql % q, q);
-            uint64_t* d = &rs[((size_t)l * L0 + i) * 4];
-            d[0] = inv; d[1] = h_shoup(inv, q); d[2] = half % q; d[3] = half;
-        }
-    }
-    // ---- 2^e mod q for exact double reduction
-    std::vector<uint64_t> pow2((size_t)K * 1088);
-    for (int i = 0; i < K; ++i) {
-        uint64_t v = 1 % primes[i];
-        for (int e = 0; e < 1088; ++e) {
-            pow2[(size_t)i * 1088 + e] = v;
-            v = h_mulmod(v, 2, primes[i]);
-        }
-    }
-    auto up = [&](const void* src, size_t bytes, const void** dst) -> hipError_t {
-        void* d = nullptr;
-        hipError_t e = hipMalloc(&d, bytes);
-        if (e != hipSuccess) return e;
-        c->tables.push_back(d);
-        e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
-        *dst = d;
-        return e;
-    };
     DevTables& T = c->T;
-    T.N = (int)N; T.logN = c->logN; T.L0 = L0; T.P = P; T.K = K; T.dnum = dnum;
-    T.max_qbits = 0;
-    for (int i = 0; i < K; ++i) T.max_qbits = std::max(T.max_qbits, 64 - __builtin_clzll(c->q[i]));
-    // ModUp's specialised conversion: 3-limb digits with every target on the pseudo-Mersenne fold (the
-    // generic loop is then not compiled into the kernel), one-limb digits, or the generic loop
-    bool all_cpm = true;
-    for (int i = 0; i < K; ++i) all_cpm = all_cpm && ((pk[i].pm >> 40) & 1);
-    bool small_e1 = true;   // the X form's weight 2^60 mod m below 2^30 for every prime (modup_xform_tables)
-    for (int i = 0; i < K && P == 3; ++i) small_e1 = small_e1 && mu_xt[(size_t)i * 4] < (1ull << 30);
-    T.modup_dp = (P == 3 && L0 % 3 == 0 && all_cpm && small_e1) ? 3 : (P == 1 ? 1 : 0);
-    T.md_xform = T.modup_dp == 3 && md_x_ok;
-    // every prime 2^59 - d with d < 2^27 (SEAL's 59-bit Create() primes at N <= 65536): the X-form
-    // conversions reduce with compile-time folds (convert3x_b59)
-    bool b59 = T.modup_dp == 3;
-    for (int i = 0; i < K && b59; ++i) b59 = b59_prime(c->q[i]);
-    T.conv_b59 = b59;
-    bool all59 = true;
-    for (int i = 0; i < K && all59; ++i) all59 = b59_prime(c->q[i]);
-    T.all_b59 = all59;
-    // the B59 kernels compile the forward NTT's lazy mode in for N <= 16384 (fhs_kernels.hip lazy_of): every
-    // prime must carry the lazy bit there, which q < 2^59 implies -- checked, not assumed
-    for (int i = 0; i < K && (b59 || all59) && c->logN <= 14; ++i)
-        if (!((pk[i].pm >> 7) & 1))
-            return fail(FHS_ERR_INVALID, "context: a 59-bit prime without the lazy NTT bound (internal)");
-    HIPCHK(up(pk.data(), sizeof(PrimeK) * K, &T.primes), "tables");
-    HIPCHK(up(twf.data(), 8 * twf.size(), (const void**)&T.tw_fwd), "tables");
-    HIPCHK(up(twi.data(), 8 * twi.size(), (const void**)&T.tw_inv), "tables");
-    HIPCHK(up(mu_intt.data(), 8 * mu_intt.size(), (const void**)&T.modup_intt), "tables");
-    HIPCHK(up(mu_hat.data(), 8 * mu_hat.size(), (const void**)&T.modup_hat), "tables");
-    HIPCHK(up(mu_R.data(), 8 * mu_R.size(), (const void**)&T.modup_R), "tables");
-    HIPCHK(up(mu_Q.data(), 8 * mu_Q.size(), (const void**)&T.modup_Q), "tables");
-    HIPCHK(up(mu_xd.data(), 8 * mu_xd.size(), (const void**)&T.modup_xd), "tables");
-    HIPCHK(up(mu_xt.data(), 8 * mu_xt.size(), (const void**)&T.modup_xt), "tables");
-    HIPCHK(up(md_xd.data(), 8 * md_xd.size(), (const void**)&T.md_xd), "tables");
-    HIPCHK(up(md_intt.data(), 8 * md_intt.size(), (const void**)&T.md_intt), "tables");
-    HIPCHK(up(md_hat.data(), 8 * md_hat.size(), (const void**)&T.md_hat), "tables");
-    HIPCHK(up(md_pinv.data(), 8 * md_pinv.size(), (const void**)&T.md_pinv), "tables");
-    HIPCHK(up(rs.data(), 8 * rs.size(), (const void**)&T.rescale), "tables");
-    HIPCHK(up(pow2.data(), 8 * pow2.size(), (const void**)&T.pow2), "tables");
-    // host encoder / decoder tables
-    c->fft_w.resize(N);
-    for (uint64_t k = 0; k < N; ++k) c->fft_w[k] = std::polar(1.0, 2.0 * M_PI * (double)k / (double)N);
-    c->dec_twist.resize(N);
-    for (uint64_t k = 0; k < N; ++k)
-        c->dec_twist[k] = {std::cos(M_PI * (double)k / (double)N), std::sin(M_PI * (double)k / (double)N)};
-    c->slot_index.resize(N / 2);
-    uint64_t e5 = 1;
-    for (uint64_t j = 0; j < N / 2; ++j) {
-        c->slot_index[j] = (e5 - 1) / 2;
-        e5 = (e5 * 5) & (2 * N - 1);
-    }
-    {   // GPU decoder tables (fhs_kernels.hip k_decode_fft): the host decoder's own values
-        const size_t H = N / 2;
-        std::vector<double> dw(2 * H), dt(2 * H);
-        std::vector<unsigned> dp(H);
-        for (size_t k = 0; k < H; ++k) {
-            dw[2 * k] = c->fft_w[2 * k].real();
-            dw[2 * k + 1] = c->fft_w[2 * k].imag();
-            dt[2 * k] = c->dec_twist[k].real();
-            dt[2 * k + 1] = c->dec_twist[k].imag();
-            dp[k] = (unsigned)(c->slot_index[k] >> 1);
-        }
-        HIPCHK(up(dw.data(), 8 * dw.size(), (const void**)&T.dec_w), "tables");
-        HIPCHK(up(dt.data(), 8 * dt.size(), (const void**)&T.dec_twist), "tables");
-        HIPCHK(up(dp.data(), 4 * dp.size(), (const void**)&T.dec_pos), "tables");
-    }
-    {   // GPU encoder tables (fhs_kernels.hip k_encode)
-        const size_t H = N / 2;
-        const int logH = c->logN - 1;
-        std::vector<double> ew(2 * H), et(2 * H);
-        std::vector<unsigned> ep(H);
-        for (size_t k = 0; k < H; ++k) {
-            const double th = -2.0 * M_PI * (double)k / (double)H;
-            ew[2 * k] = std::cos(th);
-            ew[2 * k + 1] = std::sin(th);
-            const double tz = -M_PI * (double)k / (double)N;
-            et[2 * k] = 2.0 / (double)N * std::cos(tz);
-            et[2 * k + 1] = 2.0 / (double)N * std::sin(tz);
-        }
-        uint64_t e5 = 1;
-        for (size_t j = 0; j < H; ++j) {
-            ep[j] = h_bitrev((uint32_t)((e5 - 1) / 4), logH);
-            e5 = (e5 * 5) & (2 * N - 1);
-        }
-        HIPCHK(up(ew.data(), 8 * ew.size(), (const void**)&T.enc_w), "tables");
-        HIPCHK(up(et.data(), 8 * et.size(), (const void**)&T.enc_twist), "tables");
-        HIPCHK(up(ep.data(), 4 * ep.size(), (const void**)&T.enc_pos), "tables");
-    }
+    T.N = H.N; T.logN = H.logN; T.L0 = H.L0; T.P = H.P; T.K = H.K; T.dnum = H.dnum;
+    T.max_qbits = H.max_qbits; T.modup_dp = H.modup_dp; T.md_xform = H.md_xform;
+    T.conv_b59 = H.conv_b59; T.all_b59 = H.all_b59;
+#define UP(field, count) \
+    HIPCHK(upload_table(c.get(), H.field.data(), sizeof(H.field[0]) * (count), (const void**)&T.field), "tables")
+#define UP_ALL(field) UP(field, H.field.size())
+    UP_ALL(primes); UP_ALL(tw_fwd); UP_ALL(tw_inv);
+    UP_ALL(modup_intt); UP_ALL(modup_hat); UP_ALL(modup_R); UP_ALL(modup_Q); UP_ALL(modup_xd); UP_ALL(modup_xt);
+    UP_ALL(md_xd); UP_ALL(md_intt); UP_ALL(md_hat); UP_ALL(md_pinv);
+    UP_ALL(rescale); UP_ALL(pow2);
+    UP_ALL(dec_w); UP(dec_twist, N / 2); UP_ALL(dec_pos);   // the GPU decoder reads the first half of the host's twists
+    UP_ALL(enc_w); UP_ALL(enc_twist); UP_ALL(enc_pos);
+#undef UP_ALL
+#undef UP
+    c->dec_twist = std::move(H.dec_twist);
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->ring), fhs_context::kRingBytes, hipHostMallocDefault),
            "staging ring");
     c->stager = fhs::Stager{c.get(), stage_h2d};
@@ -1363,6 +939,7 @@ extern "C" fhs_status fhs_context_create(uint64_t N, const uint64_t* primes, int
     return FHS_OK;
 }
 
+// Also the release of a half-built context (fhs_context_create): whatever does not exist yet is skipped.
 static void ctx_free(fhs_context* c) {
     const bool trace = getenv("FHESPEAR_TRACE_LIFETIME") != nullptr;
     if (trace)
@@ -1371,8 +948,10 @@ static void ctx_free(fhs_context* c) {
     {
         Guard g(c);
         flush(c);
-        hipStreamSynchronize(c->st);
-        ctx_sync(c);
+        if (c->st) {
+            hipStreamSynchronize(c->st);
+            ctx_sync(c);
+        }
         for (void* p : c->tables) hipFree(p);
         for (auto& kv : c->seal_corr) hipFree(kv.second);
         c->seal_corr.clear();
@@ -1395,7 +974,7 @@ static void ctx_free(fhs_context* c) {
             for (auto& pr : v) { ev_put(pr.first); ev_put(pr.second); }
         for (hipEvent_t e : c->timer_open)
             if (e) ev_put(e);
-        hipStreamDestroy(c->st);
+        if (c->st) hipStreamDestroy(c->st);
     }
     delete c;
     if (trace) fprintf(stderr, "[fhespear] context %p: freed\n", (void*)c);
@@ -2248,38 +1827,9 @@ extern "C" fhs_status fhs_encode_real_batch(fhs_context* c, const double* v, siz
 // CRT-compose l residues of each coefficient to a centred double (multi-precision, host)
 static void crt_compose(const fhs_context* c, const std::vector<uint64_t>& limbs, int l, std::vector<double>& out) {
     const size_t N = c->N;
-    const int W = l + 1;
-    std::vector<uint64_t> Q(W, 0);
-    Q[0] = 1;
-    for (int i = 0; i < l; ++i) {
-        hu128 carry = 0;
-        for (int w = 0; w < W; ++w) {
-            const hu128 t = (hu128)Q[w] * c->q[i] + carry;
-            Q[w] = (uint64_t)t;
-            carry = t >> 64;
-        }
-    }
-    std::vector<uint64_t> hat((size_t)l * W, 0), ihat(l);
-    for (int i = 0; i < l; ++i) {
-        uint64_t* h = &hat[(size_t)i * W];
-        h[0] = 1;
-        uint64_t hm = 1;
-        for (int k = 0; k < l; ++k) {
-            if (k == i) continue;
-            hu128 carry = 0;
-            for (int w = 0; w < W; ++w) {
-                const hu128 t = (hu128)h[w] * c->q[k] + carry;
-                h[w] = (uint64_t)t;
-                carry = t >> 64;
-            }
-            hm = h_mulmod(hm, c->q[k] % c->q[i], c->q[i]);
-        }
-        ihat[i] = h_inv(hm, c->q[i]);
-    }
-    std::vector<uint64_t> ihat_s(l);
-    for (int i = 0; i < l; ++i) ihat_s[i] = (uint64_t)(((hu128)ihat[i] << 64) / c->q[i]);
-    std::vector<uint64_t> halfQ(W);
-    for (int w = 0; w < W; ++w) halfQ[w] = (Q[w] >> 1) | (w + 1 < W ? Q[w + 1] << 63 : 0);
+    const CrtHost C = crt_host_consts(c->q.data(), l);
+    const int W = C.W;
+    const std::vector<uint64_t>&Q = C.Q, &hat = C.hat, &ihat = C.ihat, &ihat_s = C.ihat_s, &halfQ = C.halfQ;
     out.assign(N, 0.0);
     const unsigned nth = std::max(1u, std::min<unsigned>(std::thread::hardware_concurrency(), l <= 6 ? 8 : 32));
     std::vector<std::thread> th;
@@ -2356,124 +1906,71 @@ static int decode_limbs(const fhs_context* c, double scale, int l) {
     }
     return l;
 }
-// constants of the centred CRT over the first l limbs for the GPU composition (l <= kCrtMaxL): the
-// same Q, hat, inv-hat (+ Shoup companion) and Q/2 words crt_compose derives on the host
+// A/B and test knobs of the decoder, each read here only: FULL composes all l limbs always, HOST_CRT composes on
+// the host (crt_compose), HOST_FFT runs the slot FFT on the host (decode_slots); same doubles either way
+struct DecodeKnobs {
+    bool full, host_crt, host_fft;
+};
+static const DecodeKnobs& decode_knobs() {
+    static const DecodeKnobs k{getenv("FHESPEAR_DECODE_FULL") != nullptr, getenv("FHESPEAR_DECODE_HOST_CRT") != nullptr,
+                               getenv("FHESPEAR_DECODE_HOST_FFT") != nullptr};
+    return k;
+}
+// constants of the centred CRT over the first l <= kCrtMaxL limbs, packed for the GPU composition: the words
+// crt_compose reads on the host (crt_host_consts)
 static void crt_consts(const fhs_context* c, int l, fhs::CrtConsts& K) {
+    const CrtHost C = crt_host_consts(c->q.data(), l);
     K = fhs::CrtConsts{};
     K.l = l;
-    K.W = l + 1;
-    const int W = K.W;
-    K.Q[0] = 1;
+    K.W = C.W;
+    std::copy(C.Q.begin(), C.Q.end(), K.Q);
+    std::copy(C.halfQ.begin(), C.halfQ.end(), K.halfQ);
     for (int i = 0; i < l; ++i) {
-        hu128 carry = 0;
-        for (int w = 0; w < W; ++w) {
-            const hu128 t = (hu128)K.Q[w] * c->q[i] + carry;
-            K.Q[w] = (uint64_t)t;
-            carry = t >> 64;
-        }
-    }
-    for (int i = 0; i < l; ++i) {
-        uint64_t* h = K.hat[i];
-        h[0] = 1;
-        uint64_t hm = 1;
-        for (int k = 0; k < l; ++k) {
-            if (k == i) continue;
-            hu128 carry = 0;
-            for (int w = 0; w < W; ++w) {
-                const hu128 t = (hu128)h[w] * c->q[k] + carry;
-                h[w] = (uint64_t)t;
-                carry = t >> 64;
-            }
-            hm = h_mulmod(hm, c->q[k] % c->q[i], c->q[i]);
-        }
         K.q[i] = c->q[i];
-        K.ihat[i] = h_inv(hm, c->q[i]);
-        K.ihat_s[i] = (uint64_t)(((hu128)K.ihat[i] << 64) / c->q[i]);
+        K.ihat[i] = C.ihat[i];
+        K.ihat_s[i] = C.ihat_s[i];
+        std::copy(&C.hat[(size_t)i * C.W], &C.hat[(size_t)i * C.W] + C.W, K.hat[i]);
     }
-    for (int w = 0; w < W; ++w) K.halfQ[w] = (K.Q[w] >> 1) | (w + 1 < W ? K.Q[w + 1] << 63 : 0);
 }
-// INTT of the first lv limbs and the centred CRT composition of the first k on the GPU, checked against
-// limbs k..lv-1 (*exact = every coefficient matched them); N doubles to the host
 // The composition constants of the first kk limbs and the check tables of limbs kk..l-1 ([CrtConsts as
 // words][l - kk vtabs of kCrtVtabWords]), built once per (kk, l) and kept in the context: a client decodes
 // the same few levels over and over
+constexpr size_t kCrtConstWords = sizeof(fhs::CrtConsts) / 8;
+static_assert(sizeof(fhs::CrtConsts) % 8 == 0, "CrtConsts packs into words");
 static const std::vector<uint64_t>& crt_tables(fhs_context* c, int kk, int l) {
     std::vector<uint64_t>& tab = c->crt_cache[std::make_pair(kk, l)];
     if (!tab.empty()) return tab;
-    constexpr size_t KW = sizeof(fhs::CrtConsts) / 8;
-    static_assert(sizeof(fhs::CrtConsts) % 8 == 0, "CrtConsts packs into words");
     fhs::CrtConsts K;
     crt_consts(c, kk, K);
-    tab.assign(KW + (size_t)(l - kk) * fhs::kCrtVtabWords, 0);
+    tab.assign(kCrtConstWords + (size_t)(l - kk) * fhs::kCrtVtabWords, 0);
     std::memcpy(tab.data(), &K, sizeof(K));
-    for (int x = 0; x < l - kk; ++x) {
-        uint64_t* v = tab.data() + KW + (size_t)x * fhs::kCrtVtabWords;
-        const uint64_t q = c->q[kk + x];
-        const hu128 R = (~(hu128)0) / q;
-        v[0] = q;
-        v[1] = (uint64_t)R;
-        v[2] = (uint64_t)(R >> 64);
-        const uint64_t t64 = (uint64_t)((((hu128)1) << 64) % q);
-        uint64_t pw = 1 % q;
-        for (int w = 0; w < K.W; ++w) {
-            v[3 + w] = pw;
-            pw = h_mulmod(pw, t64, q);
-        }
-    }
+    for (int x = 0; x < l - kk; ++x)
+        crt_check_table(c->q[kk + x], K.W, tab.data() + kCrtConstWords + (size_t)x * fhs::kCrtVtabWords);
     return tab;
 }
-static fhs_status decode_coeffs_dev(fhs_context* c, const fhs_plaintext* pt, int k, int lv, std::vector<double>& m,
-                                    bool* exact) {
-    const size_t N = c->N, bytes = 8ull * lv * N;
-    const int nx = lv - k;
-    constexpr size_t KW = sizeof(fhs::CrtConsts) / 8;
-    const std::vector<uint64_t>& tab = crt_tables(c, k, lv);   // [CrtConsts of k limbs][nx check tables]
-    fhs::CrtConsts K;
-    std::memcpy(&K, tab.data(), sizeof(K));
-    const uint64_t* vt = tab.data() + KW;
-    const size_t vt_words = tab.size() - KW;
-    DevTmp tmp(c), dbl(c), aux(c);   // aux: the check tables, then the mismatch flag
-    HIPCHK(tmp.alloc(bytes), "decode");
-    HIPCHK(dbl.alloc(8 * N), "decode");
-    HIPCHK(aux.alloc(8 * vt_words + 8), "decode");
-    unsigned* flag = reinterpret_cast<unsigned*>(aux.p + vt_words);
-    unsigned hflag = 0;
-    PT_DENSE(pd, pt, "decode");
-    HIPCHK(hipMemcpyAsync(tmp.p, pd, bytes, hipMemcpyDeviceToDevice, c->st), "decode");
-    if (nx > 0) HIPCHK(stage_h2d(c, aux.p, vt, 8 * vt_words), "decode");
-    HIPCHK(hipMemsetAsync(flag, 0, 4, c->st), "decode");
-    HIPCHK(fhs::launch_ntt_inv(c->T, tmp.p, lv, lv, 1, 0, c->st), "decode");
-    HIPCHK(fhs::launch_crt_compose(K, tmp.p, dbl.as<double>(), (int)N, c->st, tmp.p + (size_t)k * N, nx, aux.p, flag),
-           "decode");
-    m.resize(N);
-    HIPCHK(hipMemcpyAsync(m.data(), dbl.p, 8 * N, hipMemcpyDeviceToHost, c->st), "decode");
-    HIPCHK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, c->st), "decode");
-    HIPCHK(hipStreamSynchronize(c->st), "decode");
-    *exact = hflag == 0;
-    return FHS_OK;
-}
-static fhs_status decode_coeffs(fhs_context* c, const fhs_plaintext* pt, int k, std::vector<uint64_t>& host) {
+// Centred coefficients of the first k limbs as doubles: the INTT, then the composition on the GPU up to kCrtMaxL
+// limbs, else (or with FHESPEAR_DECODE_HOST_CRT=1) on the host from the limbs -- same arithmetic, same doubles
+static fhs_status decode_compose(fhs_context* c, const fhs_plaintext* pt, int k, std::vector<double>& m) {
     const size_t N = c->N, bytes = 8ull * k * N;
-    PT_DENSE(pd, pt, "decode");
-    DevTmp tmp(c);
+    const bool dev = k <= fhs::kCrtMaxL && !decode_knobs().host_crt;
+    DevTmp tmp(c), dbl(c);
     HIPCHK(tmp.alloc(bytes), "decode");
+    if (dev) HIPCHK(dbl.alloc(8 * N), "decode");
+    PT_DENSE(pd, pt, "decode");
     HIPCHK(hipMemcpyAsync(tmp.p, pd, bytes, hipMemcpyDeviceToDevice, c->st), "decode");
     HIPCHK(fhs::launch_ntt_inv(c->T, tmp.p, k, k, 1, 0, c->st), "decode");
-    host.resize((size_t)k * N);
-    HIPCHK(hipMemcpyAsync(host.data(), tmp.p, bytes, hipMemcpyDeviceToHost, c->st), "decode");
+    std::vector<uint64_t> host(dev ? 0 : (size_t)k * N);
+    m.resize(N);
+    if (dev) {
+        fhs::CrtConsts K;
+        std::memcpy(&K, crt_tables(c, k, k).data(), sizeof(K));
+        HIPCHK(fhs::launch_crt_compose(K, tmp.p, dbl.as<double>(), (int)N, c->st), "decode");
+        HIPCHK(hipMemcpyAsync(m.data(), dbl.p, 8 * N, hipMemcpyDeviceToHost, c->st), "decode");
+    } else {
+        HIPCHK(hipMemcpyAsync(host.data(), tmp.p, bytes, hipMemcpyDeviceToHost, c->st), "decode");
+    }
     HIPCHK(hipStreamSynchronize(c->st), "decode");
-    return FHS_OK;
-}
-// centred coefficients of the first k limbs as doubles: composed on the GPU up to kCrtMaxL limbs (same
-// arithmetic, same doubles as the host composition, which FHESPEAR_DECODE_HOST_CRT=1 forces)
-static fhs_status decode_compose(fhs_context* c, const fhs_plaintext* pt, int k, std::vector<double>& m) {
-    static const bool host_crt = getenv("FHESPEAR_DECODE_HOST_CRT") != nullptr;   // A/B and test knob
-    bool unused;
-    if (k <= fhs::kCrtMaxL && !host_crt) return decode_coeffs_dev(c, pt, k, k, m, &unused);
-    std::vector<uint64_t> host;
-    const fhs_status s = decode_coeffs(c, pt, k, host);
-    if (s != FHS_OK) return s;
-    crt_compose(c, host, k, m);
+    if (!dev) crt_compose(c, host, k, m);
     return FHS_OK;
 }
 // slots z_j = m(zeta^(5^j)) = sum_{k < N/2} (m_k + i m_{k+N/2}) zeta^k omega^(s_j k), omega = zeta^4,
@@ -2507,174 +2004,229 @@ static hipError_t readback_buf(fhs_context* c, size_t bytes, double** out) {
     return hipSuccess;
 }
 
-// Decode `count` plaintexts to their first `nslots` slots (out: count x nslots x (re, im)), all on the GPU:
-// per plaintext the INTT, centred CRT composition of the limbs the scale needs (+1) and the check against
-// the rest (decode_coeffs_dev's arithmetic); then one k_decode_fft + gather over all of them; only the
-// slots come back, through the pinned readback buffer, after ONE synchronisation.  A plaintext whose
-// check fails (an aliased coefficient) or that needs more limbs than the GPU composition takes is
-// composed exactly from all its limbs (decode_compose) and decoded on its own.  FHESPEAR_DECODE_HOST_FFT=1
-// runs the slot FFT on the host instead (decode_slots: the same operations, so the same doubles; A/B and
-// test knob).
-// cts non-null (with sk): the items are ciphertexts, decrypted straight into the INTT's buffer
-// (fhs_decrypt_decode_batch) instead of plaintexts copied there
-static fhs_status decode_many(fhs_context* c, const fhs_plaintext* const* pts, int count, int nslots, double* re_im,
-                              const fhs_ciphertext* const* cts = nullptr, fhs_secret_key* sk = nullptr) {
-    const size_t N = c->N, n = N / 2;
-    if ((!pts && !cts) || (cts && !sk) || !re_im || count < 0 || nslots < 1 || (size_t)nslots > n)
-        return fail(FHS_ERR_INVALID, "decode: bad arguments");
-    if (cts)
-        for (int i = 0; i < count; ++i) LIVE(cts[i]);
-    auto lv = [&](int i) { return cts ? cts[i]->l : pts[i]->l; };
-    auto scl = [&](int i) { return cts ? cts[i]->scale : pts[i]->scale; };
-    if (count == 0) return FHS_OK;
-    static const bool full = getenv("FHESPEAR_DECODE_FULL") != nullptr;       // A/B and test knobs
-    static const bool host_crt = getenv("FHESPEAR_DECODE_HOST_CRT") != nullptr;
-    static const bool host_fft = getenv("FHESPEAR_DECODE_HOST_FFT") != nullptr;
-    std::vector<int> fast(count, 0), kks(count, 0);
-    size_t tmp_words = 0, vt_words = 0;
-    for (int i = 0; i < count; ++i) {
-        if (cts ? !cts[i] : !pts[i]) return fail(FHS_ERR_INVALID, "decode: null plaintext or ciphertext");
-        const int l = lv(i), k = full ? l : decode_limbs(c, scl(i), l);
-        kks[i] = std::min(l, k + 1);
-        fast[i] = kks[i] < l && kks[i] <= fhs::kCrtMaxL && !host_crt;
-        if (fast[i]) {
-            tmp_words += (size_t)l * N;
-            vt_words += (size_t)(l - kks[i]) * fhs::kCrtVtabWords;
-        }
+// What decode_many decodes: plaintexts, or (cts with sk) ciphertexts decrypted straight into the INTT's buffer
+// (fhs_decrypt_decode_batch).  Everything that differs between the two is here.
+struct DecodeSrc {
+    const fhs_plaintext* const* pts = nullptr;
+    const fhs_ciphertext* const* cts = nullptr;
+    fhs_secret_key* sk = nullptr;
+    bool ok() const { return cts ? sk != nullptr : pts != nullptr; }
+    bool null_at(int i) const { return cts ? !cts[i] : !pts[i]; }
+    fhs_status live(int i) const { return cts ? live_ct(cts[i]) : FHS_OK; }
+    int l(int i) const { return cts ? cts[i]->l : pts[i]->l; }
+    double scale(int i) const { return cts ? cts[i]->scale : pts[i]->scale; }
+    // one launch brings all `count` items (at one level) to coefficient form's buffer: ciphertexts of one component
+    // count, through a staged array of their addresses (ptr_words words, written by ptrs)
+    bool batched(int count) const {
+        for (int i = 0; cts && i < count; ++i)
+            if (cts[i]->ncomp != cts[0]->ncomp) return false;
+        return cts != nullptr;
     }
-    // aux (one staged copy up to the flags): the scales, every fast item's check table (vtab), its
-    // composition job (fhs::CrtJob), the ciphertext pointers (cts), the zeroed check flags, then the slots;
-    // flags and slots come back in one copy
-    constexpr size_t JW = sizeof(fhs::CrtJob) / 8;
-    static_assert(sizeof(fhs::CrtJob) % 8 == 0, "CrtJob packs into words");
-    int nf = 0, lf = -1, max_nx = 0;
-    bool one_l = true, one_nc = true;
-    for (int i = 0; i < count; ++i) {
-        if (!fast[i]) continue;
-        one_l &= lf < 0 || lv(i) == lf;
-        one_nc &= !cts || cts[i]->ncomp == cts[0]->ncomp;
-        lf = lv(i);
-        max_nx = std::max(max_nx, lv(i) - kks[i]);
-        ++nf;
+    size_t ptr_words(int count) const { return cts ? (size_t)count : 0; }
+    void ptrs(int count, uint64_t* w) const {
+        for (int i = 0; cts && i < count; ++i) w[i] = reinterpret_cast<uint64_t>(cts[i]->d);
     }
-    const size_t FW = ((size_t)count + 1) / 2, J0 = (size_t)count + vt_words, P0 = J0 + (size_t)nf * JW,
-                 A0 = P0 + (cts ? (size_t)count : 0);
-    const size_t slot_words = host_fft ? 0 : 2 * (size_t)nslots * count;
-    const size_t aux_words = A0 + FW + slot_words;
-    HostTrace ht;
-    const size_t per_out = host_fft ? N : 2 * (size_t)nslots;   // doubles back per item
-    DevTmp tmp_h(c), dbl_h(c), aux_h(c), spec_h(c);
-    double* rb = nullptr;
-    hipError_t e = readback_buf(c, 8 * (FW + per_out * count), &rb);
-    if (e == hipSuccess && tmp_words) e = tmp_h.alloc(8 * tmp_words);
-    if (e == hipSuccess) e = dbl_h.alloc(8 * N * count);
-    if (e == hipSuccess) e = aux_h.alloc(8 * aux_words);
-    if (e == hipSuccess && !host_fft) e = spec_h.alloc(16 * n * count);
-    uint64_t *const tmp = tmp_h.p, *const dbl = dbl_h.p, *const aux = aux_h.p, *const spec = spec_h.p;
-    const unsigned* hflag = reinterpret_cast<const unsigned*>(rb);
-    double* rslots = rb + FW;
-    const double* dscales = reinterpret_cast<const double*>(aux);
-    unsigned* dflag = reinterpret_cast<unsigned*>(aux + A0);
-    uint64_t* dout = aux + A0 + FW;
-    std::vector<uint64_t> head(A0 + FW, 0);
+    hipError_t all_to(fhs_context* c, const uint64_t* ptrs_dev, int count, int lv, uint64_t* dst) const {
+        return fhs::launch_decrypt_many(c->T, reinterpret_cast<const fhs::u64* const*>(ptrs_dev), count, cts[0]->ncomp,
+                                        sk->s, dst, (size_t)lv * c->N, lv, c->st);
+    }
+    // item i's l(i) limbs (NTT form) to dst: decrypted there, or copied
+    hipError_t item_to(fhs_context* c, int i, uint64_t* dst) const {
+        if (cts) return fhs::launch_decrypt(c->T, cts[i]->d, cts[i]->ncomp, sk->s, dst, cts[i]->l, c->st);
+        const uint64_t* pd = nullptr;
+        const hipError_t e = pt_dense(c, pts[i], &pd);
+        return e != hipSuccess ? e : hipMemcpyAsync(dst, pd, 8ull * pts[i]->l * c->N, hipMemcpyDeviceToDevice, c->st);
+    }
+    // item i's coefficients composed exactly from all its limbs (of the decrypted plaintext)
+    fhs_status exact(fhs_context* c, int i, std::vector<double>& m) const {
+        if (!cts) return decode_compose(c, pts[i], pts[i]->l, m);
+        Pt pt;
+        const fhs_status s = fhs_decrypt(c, sk, cts[i], &pt.p);
+        return s != FHS_OK ? s : decode_compose(c, pt.p, pt->l, m);
+    }
+};
+// Everything decode_many decides before it touches the device.  aux is one device buffer of words: [scales:
+// count][check tables (vtab) of the fast items][one fhs::CrtJob per fast item][source pointers][check flags: FW
+// words, zeroed][slots]; all of it before the slots is staged from the host in one copy (decode_head), and flags +
+// slots come back in one copy to the pinned read-back buffer: [flags: FW words][per_out doubles per item].
+constexpr size_t kCrtJobWords = sizeof(fhs::CrtJob) / 8;
+static_assert(sizeof(fhs::CrtJob) % 8 == 0, "CrtJob packs into words");
+struct DecodePlan {
+    int count = 0, nslots = 0;
+    bool host_fft = false;
+    std::vector<int> kk;                   // limbs item i composes: what its scale needs + 1, at most its level
+    std::vector<char> fast;                // item i composes kk[i] < l limbs on the GPU, checked against the rest
+    std::vector<size_t> tmp_at, vtab_at;   // fast item i: its limbs in tmp, its check tables in aux (words)
+    int nf = 0, lf = -1, max_nx = 0;       // the fast items: how many, their (last) level, the most check limbs
+    bool one_l = true;                     // the fast items share level lf: one INTT launch over all of them
+    size_t tmp_words = 0;                  // the fast items' limbs side by side
+    size_t jobs0 = 0, ptrs0 = 0, flags0 = 0, FW = 0, slot_words = 0, aux_words = 0;
+    size_t per_out = 0;                    // doubles back per item: its slots, or (host FFT) its N coefficients
+};
+static bool decode_plan(const fhs_context* c, const DecodeSrc& src, int count, int nslots, DecodePlan& P) {
+    const DecodeKnobs& knob = decode_knobs();
+    const size_t N = c->N;
+    P.count = count;
+    P.nslots = nslots;
+    P.host_fft = knob.host_fft;
+    P.kk.assign(count, 0);
+    P.fast.assign(count, 0);
+    P.tmp_at = P.vtab_at = std::vector<size_t>(count, 0);
+    size_t vtab_end = (size_t)count;   // the check tables follow the scales
     for (int i = 0; i < count; ++i) {
-        const double sc = scl(i);
+        if (src.null_at(i)) return false;
+        const int l = src.l(i), k = knob.full ? l : decode_limbs(c, src.scale(i), l);
+        P.kk[i] = std::min(l, k + 1);
+        P.fast[i] = P.kk[i] < l && P.kk[i] <= fhs::kCrtMaxL && !knob.host_crt;
+        if (!P.fast[i]) continue;
+        P.one_l &= P.lf < 0 || l == P.lf;
+        P.lf = l;
+        P.max_nx = std::max(P.max_nx, l - P.kk[i]);
+        P.tmp_at[i] = P.tmp_words;
+        P.vtab_at[i] = vtab_end;
+        P.tmp_words += (size_t)l * N;
+        vtab_end += (size_t)(l - P.kk[i]) * fhs::kCrtVtabWords;
+        ++P.nf;
+    }
+    P.jobs0 = vtab_end;
+    P.ptrs0 = P.jobs0 + (size_t)P.nf * kCrtJobWords;
+    P.flags0 = P.ptrs0 + src.ptr_words(count);
+    P.FW = ((size_t)count + 1) / 2;
+    P.slot_words = P.host_fft ? 0 : 2 * (size_t)nslots * count;
+    P.aux_words = P.flags0 + P.FW + P.slot_words;
+    P.per_out = P.host_fft ? N : 2 * (size_t)nslots;
+    return true;
+}
+// The device and pinned buffers of one decode_many call, and the plan's regions of them
+struct DecodeBufs {
+    DevTmp tmp, dbl, aux, spec;   // limbs of the fast items; count x N coefficients; see DecodePlan; FFT scratch
+    double* rb = nullptr;         // the context's pinned read-back buffer
+    explicit DecodeBufs(fhs_context* c) : tmp(c), dbl(c), aux(c), spec(c) {}
+    const double* scales() const { return aux.as<double>(); }
+    unsigned* flags(const DecodePlan& P) const { return reinterpret_cast<unsigned*>(aux.p + P.flags0); }
+    double* slots(const DecodePlan& P) const { return reinterpret_cast<double*>(aux.p + P.flags0 + P.FW); }
+    double* rb_item(const DecodePlan& P, int i) const { return rb + P.FW + (size_t)i * P.per_out; }
+};
+// The host image of aux up to the slots, once the buffers exist: the jobs point into them
+static std::vector<uint64_t> decode_head(fhs_context* c, const DecodeSrc& src, const DecodePlan& P, const DecodeBufs& B) {
+    std::vector<uint64_t> head(P.flags0 + P.FW, 0);
+    size_t job = P.jobs0;
+    for (int i = 0; i < P.count; ++i) {
+        const double sc = src.scale(i);
         std::memcpy(&head[i], &sc, 8);
-    }
-    size_t vo = (size_t)count, jo = J0, to = 0;
-    for (int i = 0; i < count; ++i) {
-        if (!fast[i]) continue;
-        const int l = lv(i), kk = kks[i], nx = l - kk;
-        const std::vector<uint64_t>& tab = crt_tables(c, kk, l);   // [CrtConsts][nx vtabs], cached per (kk, l)
+        if (!P.fast[i]) continue;
+        const int kk = P.kk[i], nx = src.l(i) - kk;
+        const std::vector<uint64_t>& tab = crt_tables(c, kk, src.l(i));   // [CrtConsts][nx vtabs], cached per (kk, l)
         fhs::CrtJob J{};
         std::memcpy(&J.K, tab.data(), sizeof(fhs::CrtConsts));
-        std::memcpy(head.data() + vo, tab.data() + sizeof(fhs::CrtConsts) / 8, 8 * (size_t)nx * fhs::kCrtVtabWords);
-        J.limbs = tmp + to;
-        J.out = reinterpret_cast<double*>(dbl) + (size_t)i * N;
-        J.extra = tmp + to + (size_t)kk * N;
-        J.vtab = aux + vo;
-        J.flag = dflag + i;
+        std::memcpy(&head[P.vtab_at[i]], tab.data() + kCrtConstWords, 8 * (size_t)nx * fhs::kCrtVtabWords);
+        J.limbs = B.tmp.p + P.tmp_at[i];
+        J.out = B.dbl.as<double>() + (size_t)i * c->N;
+        J.extra = J.limbs + (size_t)kk * c->N;
+        J.vtab = B.aux.p + P.vtab_at[i];
+        J.flag = B.flags(P) + i;
         J.nx = nx;
-        std::memcpy(head.data() + jo, &J, sizeof(J));
-        vo += (size_t)nx * fhs::kCrtVtabWords;
-        jo += JW;
-        to += (size_t)l * N;
+        std::memcpy(&head[job], &J, sizeof(J));
+        job += kCrtJobWords;
     }
-    if (cts)
-        for (int i = 0; i < count; ++i) head[P0 + i] = reinterpret_cast<uint64_t>(cts[i]->d);
-    if (e == hipSuccess) e = stage_h2d(c, aux, head.data(), 8 * head.size());
-    // coefficient form: the fast items side by side (decrypted there, or copied), one INTT launch over all
-    // of them when they share a level (the usual client batch), else one per item
-    if (cts && nf == count && one_l && one_nc) {
-        if (e == hipSuccess)
-            e = fhs::launch_decrypt_many(c->T, reinterpret_cast<const fhs::u64* const*>(aux + P0), count, cts[0]->ncomp,
-                                         sk->s, tmp, (size_t)lf * N, lf, c->st);
+    src.ptrs(P.count, &head[P.ptrs0]);
+    return head;
+}
+// Allocate, stage, bring the fast items to coefficient form (side by side: one INTT launch over all of them when
+// they share a level -- the usual client batch -- else one per item), compose and check them, the slot FFT over
+// every item (a slow one's slots are recomputed by decode_exact_item), one copy back, ONE synchronisation.
+static fhs_status decode_enqueue(fhs_context* c, const DecodeSrc& src, const DecodePlan& P, DecodeBufs& B,
+                                 HostTrace& ht) {
+    const size_t N = c->N;
+    const int count = P.count;
+    HIPCHK(readback_buf(c, 8 * (P.FW + P.per_out * count), &B.rb), "decode");
+    if (P.tmp_words) HIPCHK(B.tmp.alloc(8 * P.tmp_words), "decode");
+    HIPCHK(B.dbl.alloc(8 * N * count), "decode");
+    HIPCHK(B.aux.alloc(8 * P.aux_words), "decode");
+    if (!P.host_fft) HIPCHK(B.spec.alloc(16 * (N / 2) * count), "decode");
+    const std::vector<uint64_t> head = decode_head(c, src, P, B);
+    HIPCHK(stage_h2d(c, B.aux.p, head.data(), 8 * head.size()), "decode");
+    if (P.nf == count && P.one_l && src.batched(count)) {
+        HIPCHK(src.all_to(c, B.aux.p + P.ptrs0, count, P.lf, B.tmp.p), "decode");
     } else {
-        to = 0;
-        for (int i = 0; e == hipSuccess && i < count; ++i) {
-            if (!fast[i]) continue;
-            const int l = lv(i);
-            const uint64_t* pd = nullptr;
-            if (!cts) e = pt_dense(c, pts[i], &pd);
-            if (e == hipSuccess)
-                e = cts ? fhs::launch_decrypt(c->T, cts[i]->d, cts[i]->ncomp, sk->s, tmp + to, l, c->st)
-                        : hipMemcpyAsync(tmp + to, pd, 8ull * l * N, hipMemcpyDeviceToDevice, c->st);
-            if (e == hipSuccess && !one_l) e = fhs::launch_ntt_inv(c->T, tmp + to, l, l, 1, 0, c->st);
-            to += (size_t)l * N;
+        for (int i = 0; i < count; ++i) {
+            if (!P.fast[i]) continue;
+            HIPCHK(src.item_to(c, i, B.tmp.p + P.tmp_at[i]), "decode");
+            if (!P.one_l) HIPCHK(fhs::launch_ntt_inv(c->T, B.tmp.p + P.tmp_at[i], src.l(i), src.l(i), 1, 0, c->st), "decode");
         }
     }
-    if (e == hipSuccess && nf > 0 && one_l) e = fhs::launch_ntt_inv(c->T, tmp, lf, lf, nf, (size_t)lf * N, c->st);
-    if (e == hipSuccess && nf > 0)
-        e = fhs::launch_crt_compose_jobs(reinterpret_cast<const fhs::CrtJob*>(aux + J0), nf, max_nx, (int)N, c->st);
-    // the slots of every item (a slow one's are recomputed below), then flags + slots in one copy back
-    if (e == hipSuccess && !host_fft)
-        e = fhs::launch_decode_slots(c->T, reinterpret_cast<const double*>(dbl), dscales, count,
-                                     reinterpret_cast<double*>(spec), nslots, reinterpret_cast<double*>(dout), c->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(rb, dflag, 8 * (FW + slot_words), hipMemcpyDeviceToHost, c->st);
-    if (e == hipSuccess && host_fft) e = hipMemcpyAsync(rslots, dbl, 8 * per_out * count, hipMemcpyDeviceToHost, c->st);
+    if (P.nf > 0 && P.one_l) HIPCHK(fhs::launch_ntt_inv(c->T, B.tmp.p, P.lf, P.lf, P.nf, (size_t)P.lf * N, c->st), "decode");
+    if (P.nf > 0)
+        HIPCHK(fhs::launch_crt_compose_jobs(reinterpret_cast<const fhs::CrtJob*>(B.aux.p + P.jobs0), P.nf, P.max_nx, (int)N,
+                                            c->st), "decode");
+    if (!P.host_fft)
+        HIPCHK(fhs::launch_decode_slots(c->T, B.dbl.as<double>(), B.scales(), count, B.spec.as<double>(), P.nslots,
+                                        B.slots(P), c->st), "decode");
+    HIPCHK(hipMemcpyAsync(B.rb, B.flags(P), 8 * (P.FW + P.slot_words), hipMemcpyDeviceToHost, c->st), "decode");
+    if (P.host_fft)
+        HIPCHK(hipMemcpyAsync(B.rb_item(P, 0), B.dbl.p, 8 * P.per_out * count, hipMemcpyDeviceToHost, c->st), "decode");
     ht.mark("decode: enqueue");
-    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+    HIPCHK(hipStreamSynchronize(c->st), "decode");
     ht.mark("decode: gpu");
-    fhs_status st = e == hipSuccess ? FHS_OK : hip_fail(e, "decode");
+    return FHS_OK;
+}
+// Item i again, composed exactly from all its limbs (its check failed: an aliased coefficient; or it needs more
+// limbs than the GPU composition takes): its coefficients (host FFT) or slots replace the fast path's in rb
+static fhs_status decode_exact_item(fhs_context* c, const DecodeSrc& src, const DecodePlan& P, DecodeBufs& B, int i) {
     std::vector<double> m;
-    for (int i = 0; st == FHS_OK && i < count; ++i) {
-        if (fast[i] && hflag[i] == 0) continue;
-        if (cts) {   // exact: all limbs, from the decrypted plaintext
-            Pt pt;
-            st = fhs_decrypt(c, sk, cts[i], &pt.p);
-            if (st == FHS_OK) st = decode_compose(c, pt.p, pt->l, m);
-        } else {
-            st = decode_compose(c, pts[i], pts[i]->l, m);   // exact: all limbs
-        }
-        if (st != FHS_OK) break;
-        double* slot = rslots + (size_t)i * per_out;
-        if (host_fft) {
-            std::copy(m.begin(), m.end(), slot);
-            continue;
-        }
-        double* di = reinterpret_cast<double*>(dbl) + (size_t)i * N;
-        e = hipMemcpyAsync(di, m.data(), 8 * N, hipMemcpyHostToDevice, c->st);
-        if (e == hipSuccess)
-            e = fhs::launch_decode_slots(c->T, di, dscales + i, 1, reinterpret_cast<double*>(spec), nslots,
-                                         reinterpret_cast<double*>(dout), c->st);
-        if (e == hipSuccess) e = hipMemcpyAsync(slot, dout, 8 * per_out, hipMemcpyDeviceToHost, c->st);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-        if (e != hipSuccess) st = hip_fail(e, "decode");
+    const fhs_status st = src.exact(c, i, m);
+    if (st != FHS_OK) return st;
+    if (P.host_fft) {
+        std::copy(m.begin(), m.end(), B.rb_item(P, i));
+        return FHS_OK;
     }
-    for (int i = 0; st == FHS_OK && i < count; ++i) {
+    double* di = B.dbl.as<double>() + (size_t)i * c->N;
+    HIPCHK(hipMemcpyAsync(di, m.data(), 8 * c->N, hipMemcpyHostToDevice, c->st), "decode");
+    HIPCHK(fhs::launch_decode_slots(c->T, di, B.scales() + i, 1, B.spec.as<double>(), P.nslots, B.slots(P), c->st),
+           "decode");
+    HIPCHK(hipMemcpyAsync(B.rb_item(P, i), B.slots(P), 8 * P.per_out, hipMemcpyDeviceToHost, c->st), "decode");
+    HIPCHK(hipStreamSynchronize(c->st), "decode");
+    return FHS_OK;
+}
+// Decode `count` items to their first `nslots` slots (re_im: count x nslots x (re, im)), all on the GPU: per item
+// the INTT, the centred CRT composition of the limbs the scale needs (+1) and the check against the rest; then one
+// k_decode_fft + gather over all of them; only the slots come back, through the pinned read-back buffer, after ONE
+// synchronisation.  An item whose check fails or that needs more limbs than the GPU composition takes is composed
+// exactly and decoded on its own (decode_exact_item).  FHESPEAR_DECODE_HOST_FFT=1 runs the slot FFT on the host
+// instead (decode_slots: the same operations, so the same doubles).
+static fhs_status decode_many(fhs_context* c, const DecodeSrc& src, int count, int nslots, double* re_im) {
+    if (!src.ok() || !re_im || count < 0 || nslots < 1 || (size_t)nslots > c->N / 2)
+        return fail(FHS_ERR_INVALID, "decode: bad arguments");
+    for (int i = 0; i < count; ++i) {
+        const fhs_status s = src.live(i);
+        if (s != FHS_OK) return s;
+    }
+    if (count == 0) return FHS_OK;
+    DecodePlan P;
+    if (!decode_plan(c, src, count, nslots, P)) return fail(FHS_ERR_INVALID, "decode: null plaintext or ciphertext");
+    HostTrace ht;
+    DecodeBufs B(c);
+    fhs_status st = decode_enqueue(c, src, P, B, ht);
+    if (st != FHS_OK) return st;
+    const unsigned* hflag = reinterpret_cast<const unsigned*>(B.rb);
+    for (int i = 0; i < count; ++i) {
+        if (P.fast[i] && hflag[i] == 0) continue;
+        if ((st = decode_exact_item(c, src, P, B, i)) != FHS_OK) return st;
+    }
+    for (int i = 0; i < count; ++i) {
         double* out = re_im + (size_t)i * 2 * nslots;
-        if (host_fft)
-            decode_slots(c, rslots + (size_t)i * N, scl(i), (size_t)nslots, out);
+        if (P.host_fft)
+            decode_slots(c, B.rb_item(P, i), src.scale(i), (size_t)nslots, out);
         else
-            std::memcpy(out, rslots + (size_t)i * per_out, 8 * per_out);
+            std::memcpy(out, B.rb_item(P, i), 8 * P.per_out);
     }
     ht.mark("decode: slots");
-    return st;
+    return FHS_OK;
 }
 extern "C" fhs_status fhs_decode(fhs_context* c, const fhs_plaintext* pt, double* re_im) {
     ENTER(c);
     if (!pt || !re_im) return fail(FHS_ERR_INVALID, "decode: null argument");
-    return decode_many(c, &pt, 1, (int)(c->N / 2), re_im);
+    return decode_many(c, DecodeSrc{&pt}, 1, (int)(c->N / 2), re_im);
 }
 extern "C" fhs_status fhs_decrypt_decode_batch(fhs_context* c, fhs_secret_key* sk, const fhs_ciphertext* const* cts,
                                                int count, int nslots, double* re_im) {
@@ -2682,8 +2234,8 @@ extern "C" fhs_status fhs_decrypt_decode_batch(fhs_context* c, fhs_secret_key* s
     if (!sk || !cts || !re_im || count < 0 || nslots < 1 || (size_t)nslots > c->N / 2)
         return fail(FHS_ERR_INVALID, "decrypt_decode_batch: bad arguments");
     for (int i0 = 0; i0 < count; i0 += kMaxBatch) {   // grid rows and scratch bound one launch
-        const fhs_status s = decode_many(c, nullptr, std::min(kMaxBatch, count - i0), nslots,
-                                         re_im + (size_t)i0 * 2 * nslots, cts + i0, sk);
+        const fhs_status s = decode_many(c, DecodeSrc{nullptr, cts + i0, sk}, std::min(kMaxBatch, count - i0), nslots,
+                                         re_im + (size_t)i0 * 2 * nslots);
         if (s != FHS_OK) return s;
     }
     return FHS_OK;
@@ -2696,7 +2248,7 @@ extern "C" fhs_status fhs_decode_batch(fhs_context* c, const fhs_plaintext* cons
     if (!pts || !re_im || count < 0 || nslots < 1 || (size_t)nslots > c->N / 2)
         return fail(FHS_ERR_INVALID, "decode_batch: bad arguments");
     for (int i0 = 0; i0 < count; i0 += kMaxBatch) {
-        const fhs_status s = decode_many(c, pts + i0, std::min(kMaxBatch, count - i0), nslots,
+        const fhs_status s = decode_many(c, DecodeSrc{pts + i0}, std::min(kMaxBatch, count - i0), nslots,
                                          re_im + (size_t)i0 * 2 * nslots);
         if (s != FHS_OK) return s;
     }

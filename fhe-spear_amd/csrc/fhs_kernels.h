@@ -217,15 +217,13 @@ struct CrtConsts {
     u64 hat[kCrtMaxL][kCrtMaxL + 1];
     u64 Q[kCrtMaxL + 1], halfQ[kCrtMaxL + 1];
 };
-// verify (optional, nx > 0): the composed integer x (|x| < Q_l / 2 of the first l limbs, centred) must
+hipError_t launch_crt_compose(const CrtConsts& K, const u64* limbs, double* out, int N, hipStream_t st);
+constexpr int kCrtVtabWords = 3 + kCrtMaxL + 1;   // per extra limb in vtab
+// one composition of a batch (launch_crt_compose_jobs): K, limbs and out as for launch_crt_compose, in HBM, and
+// the check (nx > 0): the composed integer x (|x| < Q_l / 2 of the first l limbs, centred) must
 // also agree with every further limb -- extra[e][n] (coefficient form) == x mod q_e for e < nx, vtab[e] =
 // {q_e, floor(2^128/q_e) lo, hi, (2^64)^w mod q_e for w < W}; any mismatch (x aliased: the coefficient is
 // too large for l limbs) sets *flag
-hipError_t launch_crt_compose(const CrtConsts& K, const u64* limbs, double* out, int N, hipStream_t st,
-                              const u64* extra = nullptr, int nx = 0, const u64* vtab = nullptr,
-                              unsigned* flag = nullptr);
-constexpr int kCrtVtabWords = 3 + kCrtMaxL + 1;   // per extra limb in vtab
-// one composition of a batch (launch_crt_compose_jobs): the arguments of launch_crt_compose in HBM
 struct CrtJob {
     CrtConsts K;
     const u64* limbs;

@@ -3277,13 +3277,12 @@ hipError_t launch_crt_compose_jobs(const CrtJob* jobs_dev, int count, int max_nx
     hipLaunchKernelGGL(k_crt_compose_jobs, dim3((N + 255) / 256, rows, count), dim3(256), 0, st, jobs_dev, N);
     return hipGetLastError();
 }
-hipError_t launch_crt_compose(const CrtConsts& K, const u64* limbs, double* out, int N, hipStream_t st, const u64* extra,
-                              int nx, const u64* vtab, unsigned* flag) {
+// the single composition is unchecked: no further limbs (nx = 0), so the kernel reads neither tables nor flag
+hipError_t launch_crt_compose(const CrtConsts& K, const u64* limbs, double* out, int N, hipStream_t st) {
     if (K.l < 1 || K.l > kCrtMaxL || K.W != K.l + 1) return hipErrorInvalidValue;
-    if (nx > 0 && (!extra || !vtab || !flag)) return hipErrorInvalidValue;
-    const int rows = nx > 0 ? (nx + kCrtCheckPer - 1) / kCrtCheckPer : 1;
-    hipLaunchKernelGGL(k_crt_compose, dim3((N + 255) / 256, rows), dim3(256), 0, st, K, limbs, out, N, extra, nx, vtab,
-                       flag);
+    hipLaunchKernelGGL(k_crt_compose, dim3((N + 255) / 256, 1), dim3(256), 0, st, K, limbs, out, N,
+                       static_cast<const u64*>(nullptr), 0, static_cast<const u64*>(nullptr),
+                       static_cast<unsigned*>(nullptr));
     return hipGetLastError();
 }
 

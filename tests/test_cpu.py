@@ -183,6 +183,55 @@ def test_product_fails_loudly_without_gpu():
         ph.context(p)
 
 
+def _bad_context_cases():
+    """name -> (N, moduli as bit sizes for N = 1024 or explicit values, special, Galois elements, message)"""
+    b = [59] * 3
+    return {
+        "N=1000": (1000, b, 1, None, "power of two"),
+        "N=128": (128, b, 1, None, "power of two"),
+        "special=0": (1024, b, 0, None, "bad special modulus size"),
+        "special>=nprimes": (1024, b, 3, None, "bad special modulus size"),
+        "L0 not a multiple of special": (1024, [59] * 5, 2, None, "multiple of special_modulus_size"),
+        "special=9": (1024, [59] * 18, 9, None, "special_modulus_size > 8"),
+        "duplicate modulus": (1024, "duplicate", 1, None, "duplicate modulus"),
+        "composite modulus": (1024, "composite", 1, None, "must be a prime"),
+        "prime not 1 mod 2N": (1024, "not 1 mod 2N", 1, None, "must be a prime"),
+        "61-bit prime": (1024, [59, 59, 61], 1, None, "must be a prime"),
+        "even galois element": (1024, b, 1, [5, 4], "invalid galois element"),
+        "galois element >= 2N": (1024, b, 1, [5, 2049], "invalid galois element"),
+    }
+
+
+@pytest.mark.parametrize("case", list(_bad_context_cases()))
+def test_context_create_rejects_bad_parameters_before_any_device_call(case):
+    """Every argument of context creation is validated before the device is looked for, so a bad one is a
+    ValueError with its own message on a machine without a GPU too (an invalid Galois element used to be checked
+    after the stream existed: RuntimeError("no HIP device") here, a leaked stream on a GPU machine)."""
+    sys.path.insert(0, str(REPO / "fhe-spear_amd" / "python"))
+    import pyPhantom as ph
+    N, mods, special, elts, msg = _bad_context_cases()[case]
+    good = [int(q) for q in ph.create_coeff_modulus(1024, [59] * 3)]
+    if mods == "duplicate":
+        mods = [good[0], good[0], good[1]]
+    elif mods == "composite":
+        mods = [good[0], good[1], 2049 * 4097]          # (2^11 + 1)(2^12 + 1) = 1 mod 2048, composite
+        assert (mods[2] - 1) % 2048 == 0
+    elif mods == "not 1 mod 2N":
+        mods = [good[0], good[1], int(ph.create_coeff_modulus(256, [30])[0])]
+        if (mods[2] - 1) % 2048 == 0:
+            mods[2] = 7
+    else:
+        mods = [int(q) for q in ph.create_coeff_modulus(1024, mods)]
+    p = ph.params(ph.scheme_type.ckks)
+    p.set_poly_modulus_degree(N)
+    p.set_special_modulus_size(special)
+    p.set_coeff_modulus(mods)
+    if elts:
+        p.set_galois_elts(elts)
+    with pytest.raises(ValueError, match=msg):
+        ph.context(p)
+
+
 # ------------------------------------------------------------------ multi-process exchange (gloo)
 def _worker(rank, world, port, q):
     import os
@@ -435,6 +484,22 @@ def test_wave_local_passes_touch_only_their_waves_elements(tmp_path):
                     f"-I{REPO / 'fhe-spear_amd/csrc'}", str(REPO / "tools/debug/wl_check.cpp"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout
+
+
+def test_context_tables_identities_under_sanitizers(tmp_path):
+    """fhs_tables.h's build_host_tables -- every table fhs_context_create uploads -- on the context shapes of the GPU
+    parity and edge-operand tests plus special = 8, built as a stand-alone host program with the address and
+    undefined-behaviour sanitizers: the hand-flattened table indices stay in bounds, and the values meet the
+    identities that define them (twiddle inverses and orders, Shoup companions, ModUp / ModDown / rescale products,
+    powers of two, Barrett constants, the dispatch flags) -- tools/debug/tables_check.cpp."""
+    import subprocess
+    exe = tmp_path / "tables_check"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    f"-I{REPO / 'tools/debug/shim'}", f"-I{REPO / 'fhe-spear_amd/csrc'}",
+                    str(REPO / "tools/debug/tables_check.cpp"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-2000:] + r.stderr[-2000:]
+    assert len(r.stdout.splitlines()) == 8 * 25 + 1, "one digest per table and shape"
 
 
 def _sm64(x):

@@ -213,6 +213,12 @@ def _op_gk_import(s):
     return np.stack([gk.export(e) for e in sorted(s.gk_np)])
 
 
+def _op_decode_fallback(s):
+    p = s.ph.plaintext_from_numpy(s.ctx, s.p_np, 1, _SC)
+    q = s.ph.plaintext_from_numpy(s.ctx, s.p_np, 1, _SC)
+    return _u64(s.enc.decode_batch(s.ctx, [p, q, q], 64))
+
+
 # name -> callable(state) returning the result's bits as an array; every object it makes dies with its frame
 _OPS = {
     "add": lambda s: s.ph.add(s.ctx, s.a, s.b).to_numpy(),
@@ -225,6 +231,10 @@ _OPS = {
     "decode": lambda s: _u64(s.enc.decode_complex_vector(s.ctx, s.pt)),
     "decode_batch": lambda s: _u64(s.enc.decode_batch(s.ctx, s.pts3, 64)),
     "decrypt_decode_batch": lambda s: _u64(s.sk.decrypt_decode_batch(s.ctx, s.cts3, 64)),
+    # uniformly random limbs: the check against the limbs not composed fails, so every item takes the exact
+    # fallback (all six limbs recomposed, decoded on its own)
+    "decode_fallback": _op_decode_fallback,
+    "decrypt_decode_fallback": lambda s: _u64(s.sk.decrypt_decode_batch(s.ctx, [s.a, s.b], 64)),
     "encrypt_symmetric": lambda s: s.fresh_sk().encrypt_symmetric(s.ctx, s.pt).to_numpy(),
     "encrypt_symmetric_batch": lambda s: np.stack([c.to_numpy() for c in
                                                    s.fresh_sk().encrypt_symmetric_batch(s.ctx, s.pts3[:2] + [s.pt])]),

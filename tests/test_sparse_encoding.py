@@ -17,7 +17,7 @@ def _bitrev(x, bits):
 
 
 def _enc_pos(N):
-    """fhs_host.hip: ep[j] = bitrev((5^j mod 2N - 1) / 4, log2(N/2))."""
+    """fhs_tables.h: enc_pos[j] = bitrev((5^j mod 2N - 1) / 4, log2(N/2))."""
     H, logH = N // 2, (N // 2).bit_length() - 1
     e5, out = 1, []
     for _ in range(H):
