@@ -57,7 +57,9 @@ struct DevTables {
 #endif
 // The key switch runs its half-limb kernels (k_ks_intt_h, k_modup_h, k_moddown_h: half a limb in LDS, two
 // workgroups per CU) from N = 512; N = 256 has only the full-limb k_ks_intt, k_modup (which reads residues +
-// counts) and k_moddown
+// counts) and k_moddown.  The launchers select on this with `if constexpr`, so only what can be launched is
+// instantiated: k_modup / k_moddown at N = 256, the _h forms from N = 512, k_ks_intt up to N = 16384 (small
+// launches)
 constexpr bool ks_uses_half(int logN) { return logN >= 9; }
 static_assert(FHS_NTT_HALF_MIN >= 9, "N = 256 runs the full-limb kernels only");
 // ModUp of level l reads the X form (k_centered_x + modup_convert3x) instead of residues + counts: full

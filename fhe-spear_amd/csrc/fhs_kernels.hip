@@ -39,8 +39,6 @@ typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 #ifndef FHS_MODUPH_RL
 #define FHS_MODUPH_RL 3        // k_modup_h: radix (log2) of the NTT register passes
 #endif
-#define FHS_MODUP_CH 4         // k_modup (full-limb form): coefficients per conversion chunk
-#define FHS_MODUP_RL 4         // k_modup (full-limb form): radix (log2) of the NTT register passes
 #define FHS_NTT_RL 3           // radix (log2) for the other NTT kernels
 #ifndef FHS_FWD_FIRST3
 #define FHS_FWD_FIRST3 1       // half-limb forward transforms at N = 32768: global stages 0-2 in registers
@@ -650,8 +648,7 @@ hipError_t launch_rescale(const DevTables& T, const u64* in, u64* out, u64* scra
 template <int LOGN>
 __global__ void __launch_bounds__((1 << LOGN) / 16) k_ks_intt(DevTables T, const u64* const* uniq, u64* acoef, int l, int U) {
     constexpr int N = 1 << LOGN, TH = N / 16;
-    __shared__ __attribute__((aligned(16))) u64 lds[LOGN > 14 ? 1 : (1 << LOGN) + (1 << LOGN) / 16];
-    if constexpr (LOGN <= 14) {   // full-limb form: N <= 16384 only (small launches, ks_intt_half())
+    __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, false>()];   // N <= 16384 (ks_intt_stage)
     const int tid = threadIdx.x;
     int i, u;
     if (!plain_tm(l, U, i, u)) return;
@@ -665,7 +662,6 @@ __global__ void __launch_bounds__((1 << LOGN) / 16) k_ks_intt(DevTables T, const
     u64* dst = acoef + ((size_t)u * l + i) * N;
 #pragma unroll
     for (int k = 0; k < 16; ++k) dst[tid + k * TH] = csub(lds[row_pad<TH>(tid, k)], P.q);
-    }
 }
 
 // k_ks_intt with half the limb in LDS (two workgroups per CU, co-resident with the half-limb ModUp
@@ -721,14 +717,6 @@ __global__ void __launch_bounds__((1 << LOGN) / 32, 4) k_ks_intt_h(DevTables T, 
         for (int k = 0; k < 4; ++k)
             bstore64(csub(x[k], q), rd, tid * 8, ((k >> 1) * NH + (c + 8 * (k & 1)) * TH) * 8);
     }
-}
-
-// k_ks_intt_h (half limb, two workgroups per CU) unless the launch has fewer workgroups than CUs
-// (e.g. the baby-step input alone, l workgroups): then the full-limb k_ks_intt halves the latency.
-template <int LOGN>
-static bool ks_intt_half(int nwg) {
-    if (LOGN <= 14 && nwg < FHS_FULL_FORM_MAX_WG) return false;
-    return ks_uses_half(LOGN);
 }
 
 // Exact centred-extension count, slow path (|frac - 1/2| < 2^-58; never seen on random data
@@ -866,14 +854,13 @@ static void launch_centered(const DevTables& T, u64* acoef, unsigned char* vout,
 }
 
 // (b1) ModUp + NTT: ext[u][j][t] = NTT_t(centred conv_{digit j -> t}(y_u)) for t outside digit
-// j, and a copy of the input limb t for t inside digit j.
+// j, and a copy of the input limb t for t inside digit j.  Full-limb form from residues + counts: N = 256 only
+// (launch_modup), one coefficient at a time.
 template <int LOGN>
 __global__ void __launch_bounds__((1 << LOGN) / 16) k_modup(DevTables T, const u64* const* uniq, const u64* acoef,
                                                             const unsigned char* vcnt, u64* ext, int l, int U) {
-    constexpr int N = 1 << LOGN, TH = N / 16;
-    __shared__ __attribute__((aligned(16))) u64 lds[ntt_half<LOGN>() ? 1 : (1 << LOGN) + (1 << LOGN) / 16];
-    if constexpr (!ntt_half<LOGN>()) {   // full-limb form: N <= 16384 only
-    const int tid = threadIdx.x;
+    constexpr int N = 1 << LOGN;
+    __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, false>()];
     const int P_ = T.P, K = T.K, E = l + P_, dn = (l + P_ - 1) / P_;
     int t, mi;
     if (!xcd_tinner(E, dn * U, t, mi)) return;
@@ -890,44 +877,18 @@ __global__ void __launch_bounds__((1 << LOGN) / 16) k_modup(DevTables T, const u
     const u64 Qm = qv[0], nsQm = qv[1];
     const unsigned char* vb = vcnt + ((size_t)u * dn + j) * N;
     const RedU R = redu(PM);
-    constexpr int CH = FHS_MODUP_CH;
-    // CH outputs per thread at a time; the digit's ns input limbs stream through a runtime loop so
-    // the CH loads of one limb are issued together (no per-element guards between loads).
-#pragma unroll 1
-    for (int half = 0; half < 16 / CH; ++half) {
-        u128 acc[CH];
-#pragma unroll
-        for (int k = 0; k < CH; ++k) acc[k] = u128{0, 0};
-        Acc3 a3[CH];
-#pragma unroll
-        for (int k = 0; k < CH; ++k) a3[k] = Acc3{0, 0, 0};
-#pragma unroll 1
-        for (int w = 0; w < ns; ++w) {   // ns <= 8 products per Acc3
-            const Split30 hw = split30(hat[(size_t)w * K]);
-            const u64* yw = yb + (size_t)w * N + half * CH * TH + tid;
-            u64 y[CH];
-#pragma unroll
-            for (int k = 0; k < CH; ++k) y[k] = yw[k * TH];
-#pragma unroll
-            for (int k = 0; k < CH; ++k) acc3_mac(a3[k], split30(y[k]), hw);
-        }
-#pragma unroll
-        for (int k = 0; k < CH; ++k) acc3_fold(acc[k], a3[k]);
-#pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            const int e = tid + (half * CH + k) * TH;
-            mac128(acc[k], (u64)(ns - vb[e]), Qm);   // + (ns - v) Q_S, then - ns Q_S below
-            lds[lds_pad(e)] = submod(reduce128(acc[k].lo, acc[k].hi, R), nsQm, m);
-        }
-    }
-    __syncthreads();
-    ntt_fwd_lds<LOGN, FHS_MODUP_RL>(lds, tid, T.tw_fwd + (size_t)pt * N * 2, m, R.lazy);
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const int e = tid + c * TH;
-        o[e] = fwd_canon(lds[row_pad<TH>(tid, c)], R);
-    }
-    }
+    fwd_limb<LOGN, FHS_NTT_RL, false>(
+        lds, threadIdx.x, T.tw_fwd + (size_t)pt * N * 2, R,
+        [&](int e) {
+            Acc3 a3 = {0, 0, 0};
+            for (int w = 0; w < ns; ++w)   // ns <= 8 products per Acc3
+                acc3_mac(a3, split30(yb[(size_t)w * N + e]), split30(hat[(size_t)w * K]));
+            u128 acc = {0, 0};
+            acc3_fold(acc, a3);
+            mac128(acc, (u64)(ns - vb[e]), Qm);   // + (ns - v) Q_S, then - ns Q_S below
+            return submod(reduce128(acc.lo, acc.hi, R), nsQm, m);
+        },
+        [&](int e, u64 v) { o[e] = v; });
 }
 
 // ModUp conversion of a full 3-limb digit from its X form (k_centered_x) into target limb `m`
@@ -1178,7 +1139,7 @@ static void launch_modup(const DevTables& T, const u64* const* uniq, const u64* 
     const int E = l + T.P, M = (l + T.P - 1) / T.P * U;
     void (*k)(DevTables, const u64* const*, const u64*, const unsigned char*, u64*, int, int);
     dim3 g(xcd_grid_q(E, M)), b((1 << LOGN) / 32);   // k_modup_h
-    if (!ks_uses_half(LOGN)) {   // residues + counts (launch_centered wrote no X form: modup_xform is false)
+    if constexpr (!ks_uses_half(LOGN)) {   // residues + counts (launch_centered wrote no X form: modup_xform is false)
         k = k_modup<LOGN>;
         g = dim3(xcd_grid(E, M));
         b = dim3((1 << LOGN) / 16);
@@ -1382,14 +1343,13 @@ __global__ void k_special_x(DevTables T, u64* ycoef, int R2) {
     yb[2 * (size_t)N] = w[2];
 }
 
-// (d) ModDown: out_c[i] = (acc_c[i] - NTT(conv_P->q_i(y_c))) * P^-1 (+ add_c)
+// (d) ModDown: out_c[i] = (acc_c[i] - NTT(conv_P->q_i(y_c))) * P^-1 (+ add_c).  Full-limb form: N = 256 only
+// (ks_moddown_stage).
 template <int LOGN>
 __global__ void __launch_bounds__((1 << LOGN) / 16) k_moddown(DevTables T, const KsItem* items, const u64* acc,
                                                               const u64* ycoef, int l, int R) {
-    constexpr int N = 1 << LOGN, TH = N / 16;
-    __shared__ __attribute__((aligned(16))) u64 lds[ntt_half<LOGN>() ? 1 : (1 << LOGN) + (1 << LOGN) / 16];
-    if constexpr (!ntt_half<LOGN>()) {   // full-limb form: N <= 16384 only
-    const int tid = threadIdx.x;
+    constexpr int N = 1 << LOGN;
+    __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, false>()];
     const int P_ = T.P, E = l + P_;
     int i, m;
     if (!plain_tm(l, 2 * R, i, m)) return;
@@ -1399,30 +1359,23 @@ __global__ void __launch_bounds__((1 << LOGN) / 16) k_moddown(DevTables T, const
     const KsItem it = items[r];
     const u64* y = ycoef + ((size_t)r * 2 + comp) * P_ * N;
     const u64 halfq = T.ks_seal ? T.md_pinv[3 * T.L0 + i] : 0;   // SEAL rounding: - floor(p/2) mod q_i
-#pragma unroll 4
-    for (int kk = 0; kk < 16; ++kk) {
-        const int e = tid + kk * TH;
-        u128 s = {0, 0};
-        for (int k = 0; k < P_; ++k) mac128(s, y[(size_t)k * N + e], T.md_hat[(size_t)k * T.L0 + i]);
-        lds[row_pad<TH>(tid, kk)] = submod(reduce128(s.lo, s.hi, P), halfq, q);
-    }
-    __syncthreads();
-    const RedU RU = redu(P);
-    ntt_fwd_lds<LOGN, FHS_NTT_RL>(lds, tid, T.tw_fwd + (size_t)i * N * 2, q, RU.lazy);
     const u64 pinv = T.md_pinv[2 * i], pinv_s = T.md_pinv[2 * i + 1];
     const u64* add = comp == 0 ? it.add0 : it.add1;
     const u64 aelt = comp == 0 ? it.elt : 1;
     u64* o = (comp == 0 ? it.out0 : it.out1) + (size_t)i * N;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const int e = tid + c * TH;
-        const u64 v = fwd_canon(lds[row_pad<TH>(tid, c)], RU);
-        const u64 a = acc[(((size_t)r * 2 + comp) * E + i) * N + e];
-        u64 res = shoup(submod(a, v, q), pinv, pinv_s, q);
-        if (add) res = addmod(res, add[(size_t)i * N + galois_src(e, aelt, LOGN)], q);
-        o[e] = res;
-    }
-    }
+    const u64* ac = acc + (((size_t)r * 2 + comp) * E + i) * N;
+    fwd_limb<LOGN, FHS_NTT_RL, false>(
+        lds, threadIdx.x, T.tw_fwd + (size_t)i * N * 2, redu(P),
+        [&](int e) {
+            u128 s = {0, 0};
+            for (int k = 0; k < P_; ++k) mac128(s, y[(size_t)k * N + e], T.md_hat[(size_t)k * T.L0 + i]);
+            return submod(reduce128(s.lo, s.hi, P), halfq, q);
+        },
+        [&](int e, u64 v) {
+            u64 res = shoup(submod(ac[e], v, q), pinv, pinv_s, q);
+            if (add) res = addmod(res, add[(size_t)i * N + galois_src(e, aelt, LOGN)], q);
+            o[e] = res;
+        });
 }
 
 // ModDown conversion of the P = 3 special limbs (coefficient form, already scaled by inv(P/p_k)) into
@@ -1725,10 +1678,18 @@ template <int LOGN>
 static void ks_intt_stage(const DevTables& T, const u64* const* uniq, int U, int l, const KsBufs& b, hipStream_t st,
                           const KTimer* tm, unsigned* zflag = nullptr) {
     FHS_TMARK(tm, KID_KS_INTT, 1, st);
-    if (ks_intt_half<LOGN>(l * U))
-        hipLaunchKernelGGL((k_ks_intt_h<LOGN>), dim3(l * U), dim3((1 << LOGN) / 32), 0, st, T, uniq, b.acoef, l, U);
-    else
-        hipLaunchKernelGGL((k_ks_intt<LOGN>), dim3(l * U), dim3((1 << LOGN) / 16), 0, st, T, uniq, b.acoef, l, U);
+    // k_ks_intt_h (half limb, two workgroups per CU, from N = 512) unless the launch has fewer workgroups than CUs
+    // (e.g. the baby-step input alone, l workgroups): then the full-limb k_ks_intt (N <= 16384) halves the latency
+    bool half = false;
+    if constexpr (ks_uses_half(LOGN)) {
+        half = LOGN > 14 || l * U >= FHS_FULL_FORM_MAX_WG;
+        if (half)
+            hipLaunchKernelGGL((k_ks_intt_h<LOGN>), dim3(l * U), dim3((1 << LOGN) / 32), 0, st, T, uniq, b.acoef, l, U);
+    }
+    if constexpr (LOGN <= 14) {
+        if (!half)
+            hipLaunchKernelGGL((k_ks_intt<LOGN>), dim3(l * U), dim3((1 << LOGN) / 16), 0, st, T, uniq, b.acoef, l, U);
+    }
     launch_centered(T, b.acoef, b.vcnt, l, U, st, zflag);
     FHS_TMARK(tm, KID_KS_INTT, 0, st);
 }
@@ -1771,7 +1732,7 @@ static hipError_t ks_moddown_stage(const DevTables& T, const KsItem* it, int R, 
     void (*k)(DevTables, const KsItem*, const u64*, const u64*, int, int);
     int nwg = l * 2 * R, threads = (1 << LOGN) / 32;   // k_moddown_h
     const bool xform = ks_uses_half(LOGN) && T.md_xform;
-    if (!ks_uses_half(LOGN)) {
+    if constexpr (!ks_uses_half(LOGN)) {
         k = k_moddown<LOGN>;
         threads = (1 << LOGN) / 16;
     } else if (xform && T.conv_b59 && LOGN == 15 && nwg < FHS_SPLIT_MAX_WG) {

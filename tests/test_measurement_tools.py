@@ -221,3 +221,27 @@ def test_plain_line_carries_the_headline_only():
     assert not {"roofline", "kernels", "cpu_baseline", "parity", "sustained", "seal_mode", "rwkv_block",
                 "cfg5_chain"} & set(res)
     json.dumps(res)
+
+
+def test_isa_dump_hash_ignores_addresses_and_sees_a_changed_instruction():
+    """isa_dump.py -hash: two kernels with the same instruction stream at different addresses (other branch-target
+    comments, another pc-relative literal for the call) hash equal; one changed operand changes the hash."""
+    import isa_dump
+
+    def kernel(addr, name, shift, pcrel):
+        return (f"{addr:016x} <{name}>:\n"
+                f"\tv_lshlrev_b32_e32 v1, {shift}, v0          // {addr:012X}: 00000000\n"
+                f"\ts_cbranch_execz 12                    // {addr + 4:012X}: BF88000C <{name}+0x38>\n"
+                f"\ts_getpc_b64 s[2:3]                    // {addr + 8:012X}: BE821C00\n"
+                f"\ts_add_u32 s2, s2, {pcrel}             // {addr + 12:012X}: 8002FF02\n"
+                f"\ts_swappc_b64 s[30:31], s[2:3]         // {addr + 20:012X}: BE9E1E02\n"
+                f"\ts_endpgm                              // {addr + 24:012X}: BF810000\n")
+
+    head = "\nfhs.co:\tfile format elf64-amdgpu\n\nDisassembly of section .text:\n\n"
+    a, b = "void fhs::k_a<14, true>(int)", "void fhs::k_b<14, true>(int)"
+    same = isa_dump.kernel_hashes(head + kernel(0x1000, a, 3, "0xffffe6c4") + "\n" + kernel(0x2100, b, 3, "0xffffd5c4"),
+                                  ["k_"])
+    assert sorted(same) == [a, b] and same[a] == same[b]
+    other = isa_dump.kernel_hashes(head + kernel(0x1000, a, 3, "0xffffe6c4") + "\n" + kernel(0x2100, b, 4, "0xffffd5c4"),
+                                   ["k_b"])
+    assert list(other) == [b] and other[b] != same[b]

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Disassemble the gfx950 code object already inside the built library (no recompilation):
-python tools/isa_dump.py [kernel-substring ...] [-loops] [-v]
+python tools/isa_dump.py [kernel-substring ...] [-loops] [-v] [-hash]
 
 Finds the clang offload bundle in libfhespear_hip.so (.hip_fatbin), extracts the
 amdgcn-amd-amdhsa--gfx950 ELF, runs llvm-objdump -d, and prints per-kernel instruction counts (and,
-with -loops, per basic block VALU counts) like tools/isa_stats.py does from a fresh -S compile."""
+with -loops, per basic block VALU counts) like tools/isa_stats.py does from a fresh -S compile.
+-hash: one line per kernel, its demangled name and the SHA-256 of its normalised instruction text, to compare
+the kernels of two builds (FHS_ISA_LIB names the other library)."""
 import collections
+import hashlib
 import os
 import re
 import struct
@@ -34,15 +37,35 @@ def code_object(lib=LIB):
     raise SystemExit("no gfx950 code object found")
 
 
-def disasm():
+def disasm(*more):
     co = "/tmp/fhs_gfx950.co"
     open(co, "wb").write(code_object())
-    return subprocess.run([OBJDUMP, "-d", "--mcpu=gfx950", "--no-show-raw-insn", co], capture_output=True,
+    return subprocess.run([OBJDUMP, "-d", "--mcpu=gfx950", "--no-show-raw-insn", *more, co], capture_output=True,
                           text=True, check=True).stdout
+
+
+def kernel_hashes(text, names):
+    """{name: sha256} over each kernel's instructions without addresses, labels and branch-target comments; negative
+    32-bit literals (0xffff....: the pc-relative offset of a call to a function placed before the kernel, which
+    moves with the layout) are masked"""
+    out = {}
+    for f in re.split(r"\n(?=[0-9a-f]+ <)", text):
+        m = re.match(r"[0-9a-f]+ <(.+)>:", f)
+        if not m or not any(n in m.group(1) for n in names):
+            continue
+        ins = [" ".join(l.split("//")[0].split()) for l in f.splitlines()[1:]]
+        ins = [re.sub(r"0xffff[0-9a-f]{4}\b", "0x?", l) for l in ins
+               if l and not l.startswith(";") and not re.fullmatch(r"<\S+>:", l)]
+        out[m.group(1)] = hashlib.sha256("\n".join(ins).encode()).hexdigest()
+    return out
 
 
 def main():
     names = [a for a in sys.argv[1:] if not a.startswith("-")] or ["k_modup_h"]
+    if "-hash" in sys.argv:
+        for name, h in sorted(kernel_hashes(disasm("-C"), names).items()):
+            print(f"{h}  {name}")
+        return
     text = disasm()
     funcs = re.split(r"\n(?=[0-9a-f]+ <)", text)
     for f in funcs:
