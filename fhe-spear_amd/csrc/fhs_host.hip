@@ -1470,6 +1470,18 @@ extern "C" fhs_status fhs_debug_fail_alloc(fhs_context* c, int nth, int* was_arm
     c->debug_fail_alloc = nth < 0 ? -1 : nth;
     return FHS_OK;
 }
+extern "C" fhs_status fhs_debug_launch_ledger(int op, char* buf, uint64_t len, uint64_t* needed) {
+    if (op == FHS_LEDGER_ARM || op == FHS_LEDGER_DISARM) {
+        fhs::ledger_arm(op == FHS_LEDGER_ARM);
+        return FHS_OK;
+    }
+    if (op != FHS_LEDGER_READ) return fail(FHS_ERR_INVALID, "debug_launch_ledger: unknown operation");
+    const std::string names = fhs::ledger_read();
+    if (needed) *needed = names.size() + 1;
+    if (!buf || len < names.size() + 1) return fail(FHS_ERR_INVALID, "debug_launch_ledger: buffer too short");
+    memcpy(buf, names.c_str(), names.size() + 1);
+    return FHS_OK;
+}
 extern "C" fhs_status fhs_ciphertext_device_ptr(const fhs_ciphertext* ct, void** dptr, uint64_t* bytes) {
     if (!ct || !dptr) return fail(FHS_ERR_INVALID, "null argument");
     fhs_context* c = ct->ctx;

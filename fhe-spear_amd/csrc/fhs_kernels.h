@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 struct PrfKey;   // fhs_modarith.h (ChaCha20 key of the secret-randomness PRF)
 
 namespace fhs {
@@ -207,7 +209,6 @@ hipError_t launch_diag_gather(const double* M1, const double* M2, int D, int G, 
 // no contraction, so the same doubles (fhs_host.hip decode_slots).  scales: device, count doubles.
 hipError_t launch_decode_slots(const DevTables& T, const double* m, const double* scales, int count, double* spec,
                                int nslots, double* out, hipStream_t st);
-hipError_t launch_encode_reduce(const DevTables& T, const double* coef, int count, u64* out, int l, hipStream_t st);
 hipError_t launch_key_prod(const DevTables& T, const u64* a, const u64* b, u64* out, int limbs, hipStream_t st);
 // Centred CRT composition of the first l <= kCrtMaxL limbs (coefficient form) of one polynomial into
 // doubles, the exact integer converted word by word from the top (the host decoder's arithmetic,
@@ -256,5 +257,11 @@ hipError_t launch_encode_int128(const DevTables& T, const int64_t* hi, const u64
 
 enum EltOp { OP_ADD = 0, OP_SUB = 1, OP_NEG = 2, OP_MULP = 3, OP_ADDP = 4, OP_SUBP = 5, OP_SUBNEG = 6 };
 enum SampleMode { SAMPLE_UNIFORM = 0, SAMPLE_TERNARY = 1, SAMPLE_CBD = 2, SAMPLE_SEEDED = 3, SAMPLE_TESTDATA = 4 };
+
+// Launch ledger (testing hook fhs_debug_launch_ledger): ledger_arm(true) clears the process-wide set of launched
+// kernels and starts recording, ledger_arm(false) stops; ledger_read() is the set as sorted names, one per line
+// ("k_modup_h<12, 3, true>\n"): the demangled kernel symbol without return type, namespace and parameter list.
+void ledger_arm(bool on);
+std::string ledger_read();
 
 }  // namespace fhs

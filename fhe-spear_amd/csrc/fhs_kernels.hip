@@ -23,6 +23,10 @@ typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 #include "fhs_buffer.h"
 
 #include <atomic>
+#include <cxxabi.h>
+#include <mutex>
+#include <set>
+#include <string>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -48,6 +52,77 @@ typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 #endif
 
 namespace fhs {
+
+// ---- launch ledger (testing hook, fhs_debug_launch_ledger): every launch of this file goes through FHS_LAUNCH,
+// which while the ledger is armed records the kernel's host function pointer; names are resolved only when the
+// ledger is read.  Disarmed, a launch pays one relaxed load.
+static std::atomic<bool> g_ledger_armed{false};
+static std::mutex g_ledger_mu;
+static std::set<const void*> g_ledger;
+static void ledger_note(const void* k) {
+    std::lock_guard<std::mutex> g(g_ledger_mu);
+    g_ledger.insert(k);
+}
+#define FHS_LAUNCH(K, ...)                                                                                 \
+    do {                                                                                                   \
+        if (g_ledger_armed.load(std::memory_order_relaxed)) ledger_note(reinterpret_cast<const void*>(K)); \
+        hipLaunchKernelGGL(K, __VA_ARGS__);                                                                \
+    } while (0)
+void ledger_arm(bool on) {
+    std::lock_guard<std::mutex> g(g_ledger_mu);
+    if (on) g_ledger.clear();
+    g_ledger_armed.store(on, std::memory_order_relaxed);
+}
+// "void fhs::k_modup_h<12, 3, true>(fhs::DevTables, ...)" -> "k_modup_h<12, 3, true>": the parameter list goes at
+// the first '(' outside <>, the return type at the last space outside <>, the namespaces at the last "::" outside <>
+static std::string ledger_normalise(const std::string& demangled) {
+    auto outside = [](const std::string& s, const char* tok, bool last) {
+        const size_t n = strlen(tok);
+        long found = -1;
+        int depth = 0;
+        for (size_t i = 0; i < s.size(); ++i) {
+            if (s[i] == '<') ++depth;
+            else if (s[i] == '>') --depth;
+            else if (depth == 0 && s.compare(i, n, tok) == 0) {
+                found = (long)i;
+                if (!last) break;
+            }
+        }
+        return found;
+    };
+    std::string s = demangled;
+    long i = outside(s, "(", false);
+    if (i >= 0) s.resize(i);
+    i = outside(s, " ", true);
+    if (i >= 0) s.erase(0, i + 1);
+    i = outside(s, "::", true);
+    if (i >= 0) s.erase(0, i + 2);
+    return s;
+}
+std::string ledger_read() {
+    std::vector<const void*> ptrs;
+    {
+        std::lock_guard<std::mutex> g(g_ledger_mu);
+        ptrs.assign(g_ledger.begin(), g_ledger.end());
+    }
+    std::set<std::string> names;
+    for (const void* p : ptrs) {
+        const char* mangled = hipKernelNameRefByPtr(p, nullptr);
+        if (!mangled || !*mangled) {
+            char buf[32];
+            snprintf(buf, sizeof buf, "?%p", p);
+            names.insert(buf);
+            continue;
+        }
+        int status = 0;
+        char* d = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+        names.insert(ledger_normalise(status == 0 && d ? d : mangled));
+        free(d);
+    }
+    std::string out;
+    for (const std::string& n : names) out += n + "\n";
+    return out;
+}
 
 #define FHS_DISPATCH_LOGN(logN, ...)                   \
     switch (logN) {                                    \
@@ -146,9 +221,9 @@ template <int LOGN, bool H = ntt_half<LOGN>()> constexpr int ntt_lds_words() {
     do {                                                                                               \
         constexpr bool FH_ = (LOGN > 14);   /* the full-limb form needs N <= 16384 */                   \
         if ((nwg) < FHS_FULL_FORM_MAX_WG && !FH_)                                                      \
-            hipLaunchKernelGGL((K<LOGN, FH_>), grid, dim3(ntt_threads<LOGN, FH_>()), 0, st, __VA_ARGS__); \
+            FHS_LAUNCH((K<LOGN, FH_>), grid, dim3(ntt_threads<LOGN, FH_>()), 0, st, __VA_ARGS__); \
         else                                                                                           \
-            hipLaunchKernelGGL((K<LOGN>), grid, dim3(ntt_threads<LOGN>()), 0, st, __VA_ARGS__);        \
+            FHS_LAUNCH((K<LOGN>), grid, dim3(ntt_threads<LOGN>()), 0, st, __VA_ARGS__);        \
     } while (0)
 // Radix-4 first stages: the half-limb forward transforms of ModUp / ModDown do global stages 0 and 1 in
 // registers while converting -- a thread's rows c and c + 8 are N/4 apart, so it converts the quad
@@ -388,8 +463,8 @@ hipError_t launch_ntt_fwd(const DevTables& T, u64* data, int limbs, int l_split,
                           hipStream_t st) {
     if (limbs <= 0 || npoly <= 0) return hipSuccess;
     FHS_DISPATCH_LOGN(T.logN, {
-        hipLaunchKernelGGL((k_ntt_fwd<LOGN>), dim3(limbs, npoly), dim3(ntt_threads<LOGN>()), 0, st, T,
-                           data, limbs, l_split, poly_stride);
+        FHS_LAUNCH((k_ntt_fwd<LOGN>), dim3(limbs, npoly), dim3(ntt_threads<LOGN>()), 0, st, T,
+                   data, limbs, l_split, poly_stride);
     });
     return hipGetLastError();
 }
@@ -397,8 +472,8 @@ hipError_t launch_ntt_inv(const DevTables& T, u64* data, int limbs, int l_split,
                           hipStream_t st) {
     if (limbs <= 0 || npoly <= 0) return hipSuccess;
     FHS_DISPATCH_LOGN(T.logN, {
-        hipLaunchKernelGGL((k_ntt_inv<LOGN>), dim3(limbs, npoly), dim3(ntt_threads<LOGN>()), 0, st, T,
-                           data, limbs, l_split, poly_stride);
+        FHS_LAUNCH((k_ntt_inv<LOGN>), dim3(limbs, npoly), dim3(ntt_threads<LOGN>()), 0, st, T,
+                   data, limbs, l_split, poly_stride);
     });
     return hipGetLastError();
 }
@@ -451,7 +526,7 @@ static inline int eltwise_grid(size_t work) {
 hipError_t launch_eltwise(const DevTables& T, int op, const u64* a, const u64* b, u64* out, int ncomp, int l,
                           size_t a_cs, size_t b_cs, hipStream_t st) {
     const size_t work = (size_t)ncomp * l * T.N / 2;
-    hipLaunchKernelGGL(k_eltwise, dim3(eltwise_grid(work)), dim3(256), 0, st, T, op, a, b, out, ncomp, l, a_cs, b_cs);
+    FHS_LAUNCH(k_eltwise, dim3(eltwise_grid(work)), dim3(256), 0, st, T, op, a, b, out, ncomp, l, a_cs, b_cs);
     return hipGetLastError();
 }
 
@@ -473,7 +548,7 @@ __global__ void k_tensor(DevTables T, const u64* __restrict__ a, const u64* __re
     }
 }
 hipError_t launch_tensor(const DevTables& T, const u64* a, const u64* b, u64* out3, int l, hipStream_t st) {
-    hipLaunchKernelGGL(k_tensor, dim3(eltwise_grid((size_t)l * T.N)), dim3(256), 0, st, T, a, b, out3, l);
+    FHS_LAUNCH(k_tensor, dim3(eltwise_grid((size_t)l * T.N)), dim3(256), 0, st, T, a, b, out3, l);
     return hipGetLastError();
 }
 
@@ -486,7 +561,7 @@ __global__ void k_key_prod(DevTables T, const u64* a, const u64* b, u64* out, in
     }
 }
 hipError_t launch_key_prod(const DevTables& T, const u64* a, const u64* b, u64* out, int limbs, hipStream_t st) {
-    hipLaunchKernelGGL(k_key_prod, dim3(eltwise_grid((size_t)limbs * T.N)), dim3(256), 0, st, T, a, b, out, limbs);
+    FHS_LAUNCH(k_key_prod, dim3(eltwise_grid((size_t)limbs * T.N)), dim3(256), 0, st, T, a, b, out, limbs);
     return hipGetLastError();
 }
 
@@ -498,8 +573,8 @@ __global__ void k_galois_perm(DevTables T, const u64* in, u64* out, int limbs, u
     }
 }
 hipError_t launch_galois_perm(const DevTables& T, const u64* in, u64* out, int limbs, u64 elt, hipStream_t st) {
-    hipLaunchKernelGGL(k_galois_perm, dim3(eltwise_grid((size_t)limbs * T.N)), dim3(256), 0, st, T, in, out, limbs,
-                       elt);
+    FHS_LAUNCH(k_galois_perm, dim3(eltwise_grid((size_t)limbs * T.N)), dim3(256), 0, st, T, in, out, limbs,
+               elt);
     return hipGetLastError();
 }
 
@@ -628,10 +703,10 @@ hipError_t launch_rescale(const DevTables& T, const u64* in, u64* out, u64* scra
     FHS_DISPATCH_LOGN(T.logN, {
         if constexpr (LOGN == 15) {
             if (ncomp <= 2) {
-                hipLaunchKernelGGL((k_rescale_intt_hs<LOGN>), dim3(2, ncomp), dim3(ntt_threads<LOGN, true>()), 0, st, T,
-                                   in, scratch, l);
-                hipLaunchKernelGGL((k_rescale_ntt_hs<LOGN>), dim3(l - 1, ncomp, 2), dim3(ntt_threads<LOGN, true>()), 0, st,
-                                   T, in, scratch, out, l);
+                FHS_LAUNCH((k_rescale_intt_hs<LOGN>), dim3(2, ncomp), dim3(ntt_threads<LOGN, true>()), 0, st, T,
+                           in, scratch, l);
+                FHS_LAUNCH((k_rescale_ntt_hs<LOGN>), dim3(l - 1, ncomp, 2), dim3(ntt_threads<LOGN, true>()), 0, st,
+                           T, in, scratch, out, l);
                 break;
             }
         }
@@ -848,9 +923,9 @@ static void launch_centered(const DevTables& T, u64* acoef, unsigned char* vout,
                             unsigned* zflag = nullptr) {
     const int dn = (l + T.P - 1) / T.P;
     if (modup_xform(T, l))
-        hipLaunchKernelGGL(k_centered_x, dim3((T.N + 255) / 256, U * dn), dim3(256), 0, st, T, acoef, l, U);
+        FHS_LAUNCH(k_centered_x, dim3((T.N + 255) / 256, U * dn), dim3(256), 0, st, T, acoef, l, U);
     else
-        hipLaunchKernelGGL(k_centered, dim3((T.N + 255) / 256, U * dn), dim3(256), 0, st, T, acoef, vout, l, U, zflag);
+        FHS_LAUNCH(k_centered, dim3((T.N + 255) / 256, U * dn), dim3(256), 0, st, T, acoef, vout, l, U, zflag);
 }
 
 // (b1) ModUp + NTT: ext[u][j][t] = NTT_t(centred conv_{digit j -> t}(y_u)) for t outside digit
@@ -1150,7 +1225,7 @@ static void launch_modup(const DevTables& T, const u64* const* uniq, const u64* 
     } else {
         k = k_modup_h<LOGN, 0, false>;
     }
-    hipLaunchKernelGGL(k, g, b, 0, st, T, uniq, acoef, vcnt, ext, l, U);
+    FHS_LAUNCH(k, g, b, 0, st, T, uniq, acoef, vcnt, ext, l, U);
 }
 
 // (b2) key inner product with the automorphism applied on the fly, lazy 128-bit over digits:
@@ -1648,7 +1723,7 @@ static hipError_t seal_permute(const DevTables& T, const KsItem* orig, int R, in
     const int gx = std::max(1, eltwise_grid(S) / 8);
     auto flush = [&]() -> hipError_t {
         if (!n) return hipSuccess;
-        hipLaunchKernelGGL(k_galois_perm_batch, dim3(gx, n), dim3(256), 0, st, T, pb, l);
+        FHS_LAUNCH(k_galois_perm_batch, dim3(gx, n), dim3(256), 0, st, T, pb, l);
         n = 0;
         return hipGetLastError();
     };
@@ -1684,11 +1759,11 @@ static void ks_intt_stage(const DevTables& T, const u64* const* uniq, int U, int
     if constexpr (ks_uses_half(LOGN)) {
         half = LOGN > 14 || l * U >= FHS_FULL_FORM_MAX_WG;
         if (half)
-            hipLaunchKernelGGL((k_ks_intt_h<LOGN>), dim3(l * U), dim3((1 << LOGN) / 32), 0, st, T, uniq, b.acoef, l, U);
+            FHS_LAUNCH((k_ks_intt_h<LOGN>), dim3(l * U), dim3((1 << LOGN) / 32), 0, st, T, uniq, b.acoef, l, U);
     }
     if constexpr (LOGN <= 14) {
         if (!half)
-            hipLaunchKernelGGL((k_ks_intt<LOGN>), dim3(l * U), dim3((1 << LOGN) / 16), 0, st, T, uniq, b.acoef, l, U);
+            FHS_LAUNCH((k_ks_intt<LOGN>), dim3(l * U), dim3((1 << LOGN) / 16), 0, st, T, uniq, b.acoef, l, U);
     }
     launch_centered(T, b.acoef, b.vcnt, l, U, st, zflag);
     FHS_TMARK(tm, KID_KS_INTT, 0, st);
@@ -1704,8 +1779,8 @@ static void ks_modup_stage(const DevTables& T, const u64* const* uniq, int U, in
 static void ks_ip_stage(const DevTables& T, const KsItem* it, const u64* const* uniq, int R, int l, const KsBufs& b,
                         hipStream_t st, const KTimer* tm) {
     FHS_TMARK(tm, KID_KS_IP, 1, st);
-    hipLaunchKernelGGL(k_ks_ip, dim3(xcd_grid(l + T.P, R * (T.N >> 8))), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R,
-                       0);
+    FHS_LAUNCH(k_ks_ip, dim3(xcd_grid(l + T.P, R * (T.N >> 8))), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R,
+               0);
     FHS_TMARK(tm, KID_KS_IP, 0, st);
 }
 // giant-step key inner product: the special limbs per rotation, the data limbs summed over the rotations
@@ -1713,8 +1788,8 @@ static void giant_ip_stage(const DevTables& T, const KsItem* it, const u64* cons
                            hipStream_t st, const KTimer* tm) {
     const int NB = T.N >> 8;
     FHS_TMARK(tm, KID_KS_IP, 1, st);
-    hipLaunchKernelGGL(k_ks_ip, dim3(T.P * R * NB), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R, l);
-    hipLaunchKernelGGL(k_ks_ip_sum, dim3(xcd_grid(l, NB)), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R);
+    FHS_LAUNCH(k_ks_ip, dim3(T.P * R * NB), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R, l);
+    FHS_LAUNCH(k_ks_ip_sum, dim3(xcd_grid(l, NB)), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R);
     FHS_TMARK(tm, KID_KS_IP, 0, st);
 }
 // special limbs of acc -> ycoef [R][2][P][N] (coefficient form)
@@ -1745,8 +1820,8 @@ static hipError_t ks_moddown_stage(const DevTables& T, const KsItem* it, int R, 
         k = T.all_b59 ? k_moddown_h<LOGN, false, true> : k_moddown_h<LOGN, false>;
     }
     if (xform)   // the special digit to its X form, then the two-product conversion
-        hipLaunchKernelGGL(k_special_x, dim3((T.N + 255) / 256, 2 * R), dim3(256), 0, st, T, b.ycoef, 2 * R);
-    hipLaunchKernelGGL(k, dim3(nwg), dim3(threads), 0, st, T, it, b.acc, b.ycoef, l, R);
+        FHS_LAUNCH(k_special_x, dim3((T.N + 255) / 256, 2 * R), dim3(256), 0, st, T, b.ycoef, 2 * R);
+    FHS_LAUNCH(k, dim3(nwg), dim3(threads), 0, st, T, it, b.acc, b.ycoef, l, R);
     FHS_TMARK(tm, KID_MODDOWN, 0, st);
     return hipGetLastError();
 }
@@ -1810,11 +1885,11 @@ __global__ void __launch_bounds__(256) k_seal_corr(DevTables T, const u64* key, 
 hipError_t launch_seal_corr(const DevTables& T, const u64* key, const u64* akey, u64 elt, int l, u64* mask_scratch,
                             u64* out, hipStream_t st) {
     if (T.P != 1 || l < 1 || l > T.L0 || !key || !out || !mask_scratch) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_seal_mask, dim3((T.N + 255) / 256), dim3(256), 0, st, T, elt, mask_scratch);
+    FHS_LAUNCH(k_seal_mask, dim3((T.N + 255) / 256), dim3(256), 0, st, T, elt, mask_scratch);
     hipError_t e = launch_ntt_fwd(T, mask_scratch, T.K, T.L0, 1, 0, st);   // limb t at prime t: l_split = L0
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_seal_corr, dim3((T.N + 255) / 256, l + T.P), dim3(256), 0, st, T, key, akey, mask_scratch,
-                       l, out);
+    FHS_LAUNCH(k_seal_corr, dim3((T.N + 255) / 256, l + T.P), dim3(256), 0, st, T, key, akey, mask_scratch,
+               l, out);
     return hipGetLastError();
 }
 
@@ -2155,7 +2230,7 @@ static hipError_t launch_inner_t(const DevTables& T, const u64* const* baby, con
         const size_t lds = (size_t)Gw * 2 * W * 8;
         const dim3 grid(T.N / W, l), block(64 * WAVES);
         const InnerFn k = inner_kernel<VEC, WAVES>(T.max_qbits <= 59, b0 > 0, ptl);
-        hipLaunchKernelGGL(k, grid, block, lds, st, T, baby + b0, pts + b0, G, Gw, g0, g1, Dw, l, inner);
+        FHS_LAUNCH(k, grid, block, lds, st, T, baby + b0, pts + b0, G, Gw, g0, g1, Dw, l, inner);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -2283,7 +2358,7 @@ static hipError_t launch_dot_t(const DevTables& T, const u64* const* q, const u6
         const size_t lds = (size_t)Jw * 2 * W * 8;
         const dim3 grid(T.N / W, l), block(64 * WAVES);
         const DotFn k = dot_kernel<VEC, WAVES>(T.max_qbits <= 59, j0 > 0);
-        hipLaunchKernelGGL(k, grid, block, lds, st, T, q + j0, db + j0, J, Jw, C, l, out);
+        FHS_LAUNCH(k, grid, block, lds, st, T, q + j0, db + j0, J, Jw, C, l, out);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -2359,8 +2434,8 @@ hipError_t launch_bsgs(const DevTables& T, const u64* const* baby_dev, const u64
         giant_ip_stage(T, it, uq, R, l, b, st, tm);
         ks_special_intt_stage<LOGN>(T, R, l, b, st, tm);
         FHS_TMARK(tm, KID_GIANT_SUM, 1, st);
-        hipLaunchKernelGGL(k_giant_sum, dim3((T.N + 255) / 256, 2, (l + FHS_GSUM_ICH - 1) / FHS_GSUM_ICH), dim3(256), 0,
-                           st, T, b.acc, b.ycoef, inner, base, convsum, l, R);
+        FHS_LAUNCH(k_giant_sum, dim3((T.N + 255) / 256, 2, (l + FHS_GSUM_ICH - 1) / FHS_GSUM_ICH), dim3(256), 0,
+                   st, T, b.acc, b.ycoef, inner, base, convsum, l, R);
         FHS_TMARK(tm, KID_GIANT_SUM, 0, st);
         FHS_TMARK(tm, KID_GIANT_FINAL, 1, st);
         FHS_NTT_LAUNCH(k_giant_final, l * 2, dim3(l, 2), st, T, base, convsum, out, l);
@@ -2416,7 +2491,7 @@ hipError_t launch_sample(const DevTables& T, int mode, const PrfKey& K, u64 sid,
                          int npoly, u64 sid_step, u64* const* outs_dev) {
     if (npoly < 1) return hipSuccess;
     const int g1 = eltwise_grid((size_t)l * T.N) / npoly, gx = g1 > 0 ? g1 : 1;
-    hipLaunchKernelGGL(k_sample, dim3(gx, npoly), dim3(256), 0, st, T, mode, K, sid, out, l, sid_step, outs_dev);
+    FHS_LAUNCH(k_sample, dim3(gx, npoly), dim3(256), 0, st, T, mode, K, sid, out, l, sid_step, outs_dev);
     return hipGetLastError();
 }
 
@@ -2437,8 +2512,8 @@ __global__ void k_swk(DevTables T, u64* b_out, const u64* a, const u64* e, const
 }
 hipError_t launch_switch_key_assemble(const DevTables& T, u64* b_out, const u64* a, const u64* e_ntt, const u64* s_ntt,
                                       const u64* snew_ntt, int digit, hipStream_t st) {
-    hipLaunchKernelGGL(k_swk, dim3(eltwise_grid((size_t)T.K * T.N)), dim3(256), 0, st, T, b_out, a, e_ntt, s_ntt,
-                       snew_ntt, digit);
+    FHS_LAUNCH(k_swk, dim3(eltwise_grid((size_t)T.K * T.N)), dim3(256), 0, st, T, b_out, a, e_ntt, s_ntt,
+               snew_ntt, digit);
     return hipGetLastError();
 }
 
@@ -2508,7 +2583,7 @@ struct DblMod {
 };
 __device__ __forceinline__ DblMod dbl_mod_of(const DevTables& T, int i) {
     const PrimeK& P = PK(T, i);
-    const u64 pm = P.pm, q = P.q;   // i may vary per lane (k_encode_reduce): no readfirstlane
+    const u64 pm = P.pm, q = P.q;   // i may vary per lane: no readfirstlane
     const unsigned b = (unsigned)(pm & 127), d = (unsigned)((pm >> 8) & 0xFFFFFFFFu);
     const bool fold1 = b != 0 && ((u64)d << (64 - b)) + (1ull << b) < 2 * q;
     return DblMod{&P, T.pow2 + (size_t)i * 1088, q, b ? (1ull << b) - 1 : 0, b, d, fold1};
@@ -2586,25 +2661,25 @@ hipError_t launch_encrypt_sym_batch(const DevTables& T, const PrfKey& K, u64 sid
                                     u64* const* cts_dev, const u64* s, const u64* const* pts_dev, int count, int l,
                                     signed char* small, u64* eb, hipStream_t st, const double* coef) {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_sample_small, dim3((T.N + 255) / 256, count), dim3(256), 0, st, (int)SAMPLE_CBD, K, sid_err,
-                       sid_step, T.N, small);
+    FHS_LAUNCH(k_sample_small, dim3((T.N + 255) / 256, count), dim3(256), 0, st, (int)SAMPLE_CBD, K, sid_err,
+               sid_step, T.N, small);
     FHS_DISPATCH_LOGN(T.logN, {
         if (coef)
-            hipLaunchKernelGGL((k_ntt_fwd_msg_err<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T, coef,
-                               static_cast<const signed char*>(small), eb, l);
+            FHS_LAUNCH((k_ntt_fwd_msg_err<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T, coef,
+                       static_cast<const signed char*>(small), eb, l);
         else
-            hipLaunchKernelGGL((k_ntt_fwd_small<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T,
-                               static_cast<const signed char*>(small), eb, l);
+            FHS_LAUNCH((k_ntt_fwd_small<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T,
+                       static_cast<const signed char*>(small), eb, l);
     });
     const int g1 = eltwise_grid((size_t)l * T.N) / count, gx = g1 > 0 ? g1 : 1;
-    hipLaunchKernelGGL(k_encrypt_sym, dim3(gx, count), dim3(256), 0, st, T, K, sid_mask, sid_step, cts_dev, s,
-                       static_cast<const u64*>(eb), pts_dev, l);
+    FHS_LAUNCH(k_encrypt_sym, dim3(gx, count), dim3(256), 0, st, T, K, sid_mask, sid_step, cts_dev, s,
+               static_cast<const u64*>(eb), pts_dev, l);
     return hipGetLastError();
 }
 hipError_t launch_encrypt_combine(const DevTables& T, int mode, u64* c0, u64* c1, const u64* s_or_pk0, const u64* pk1,
                                   const u64* u_ntt, const u64* e0, const u64* e1, const u64* pt, int l, hipStream_t st) {
-    hipLaunchKernelGGL(k_encrypt, dim3(eltwise_grid((size_t)l * T.N)), dim3(256), 0, st, T, mode, c0, c1, s_or_pk0,
-                       pk1, u_ntt, e0, e1, pt, l);
+    FHS_LAUNCH(k_encrypt, dim3(eltwise_grid((size_t)l * T.N)), dim3(256), 0, st, T, mode, c0, c1, s_or_pk0,
+               pk1, u_ntt, e0, e1, pt, l);
     return hipGetLastError();
 }
 
@@ -2646,28 +2721,12 @@ hipError_t launch_decrypt_many(const DevTables& T, const u64* const* cts_dev, in
                                size_t out_stride, int l, hipStream_t st) {
     if (count <= 0) return hipSuccess;
     const int g1 = eltwise_grid((size_t)l * T.N) / count, gx = g1 > 0 ? g1 : 1;
-    hipLaunchKernelGGL(k_decrypt_many, dim3(gx, count), dim3(256), 0, st, T, cts_dev, ncomp, s, out, out_stride, l);
+    FHS_LAUNCH(k_decrypt_many, dim3(gx, count), dim3(256), 0, st, T, cts_dev, ncomp, s, out, out_stride, l);
     return hipGetLastError();
 }
 hipError_t launch_decrypt(const DevTables& T, const u64* ct, int ncomp, const u64* s, u64* out, int l, hipStream_t st) {
-    hipLaunchKernelGGL(k_decrypt, dim3(eltwise_grid((size_t)l * T.N)), dim3(256), 0, st, T, ct, ncomp, s, out, l);
+    FHS_LAUNCH(k_decrypt, dim3(eltwise_grid((size_t)l * T.N)), dim3(256), 0, st, T, ct, ncomp, s, out, l);
     return hipGetLastError();
-}
-
-// exact residue of integral doubles: coef [count][N] -> out [count][l][N] (coefficient form)
-// exact residue of an integral double (any magnitude) mod prime i
-
-__global__ void k_encode_reduce(DevTables T, const double* coef, int count, u64* out, int l) {
-    const int N = T.N;
-    const size_t total = (size_t)count * l * N;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (size_t)gridDim.x * blockDim.x) {
-        const int n = (int)(idx % N);
-        const size_t rest = idx / N;
-        const int i = (int)(rest % l);
-        const size_t v = rest / l;
-        out[idx] = dbl_mod(T, coef[v * N + n], i);
-    }
 }
 
 // ---- CKKS encoder (pb:138-156, bg:382, 423 encode_*_vector_batch) ----
@@ -2955,11 +3014,11 @@ hipError_t launch_decode_slots(const DevTables& T, const double* m, const double
     if (count <= 0) return hipSuccess;
     if (nslots < 1 || nslots > T.N / 2) return hipErrorInvalidValue;
     FHS_DISPATCH_LOGN(T.logN, {
-        hipLaunchKernelGGL((k_decode_fft<LOGN>), dim3(count), dim3(dec_threads<LOGN>()), 0, st, T, m, scales,
-                           reinterpret_cast<double2*>(spec));
+        FHS_LAUNCH((k_decode_fft<LOGN>), dim3(count), dim3(dec_threads<LOGN>()), 0, st, T, m, scales,
+                   reinterpret_cast<double2*>(spec));
     });
-    hipLaunchKernelGGL(k_decode_gather, dim3(eltwise_grid((size_t)count * nslots)), dim3(256), 0, st, T,
-                       reinterpret_cast<const double2*>(spec), count, nslots, reinterpret_cast<double2*>(out));
+    FHS_LAUNCH(k_decode_gather, dim3(eltwise_grid((size_t)count * nslots)), dim3(256), 0, st, T,
+               reinterpret_cast<const double2*>(spec), count, nslots, reinterpret_cast<double2*>(out));
     return hipGetLastError();
 }
 
@@ -3036,15 +3095,15 @@ static void launch_ntt_fwd_sparse(const DevTables& T, const double* coef, u64* c
     static_assert(kEncSparseMaxLog == 3, "one launch per sparse factor below");
     if constexpr (LOGN - 1 >= kEncSparseMinLogM)
         if (ss <= 1)
-            hipLaunchKernelGGL((k_ntt_fwd_from_dbl_sp<LOGN, 1>), dim3(l, count), dim3(ntt_threads<LOGN - 1>()), 0, st,
-                               T, coef, outs, l, tlog, couts, ss);
+            FHS_LAUNCH((k_ntt_fwd_from_dbl_sp<LOGN, 1>), dim3(l, count), dim3(ntt_threads<LOGN - 1>()), 0, st,
+                       T, coef, outs, l, tlog, couts, ss);
     if constexpr (LOGN - 2 >= kEncSparseMinLogM)
         if (ss <= 2)
-            hipLaunchKernelGGL((k_ntt_fwd_from_dbl_sp<LOGN, 2>), dim3(l, count), dim3(ntt_threads<LOGN - 2>()), 0, st,
-                               T, coef, outs, l, tlog, couts, ss);
+            FHS_LAUNCH((k_ntt_fwd_from_dbl_sp<LOGN, 2>), dim3(l, count), dim3(ntt_threads<LOGN - 2>()), 0, st,
+                       T, coef, outs, l, tlog, couts, ss);
     if constexpr (LOGN - 3 >= kEncSparseMinLogM)
-        hipLaunchKernelGGL((k_ntt_fwd_from_dbl_sp<LOGN, 3>), dim3(l, count), dim3(ntt_threads<LOGN - 3>()), 0, st, T,
-                           coef, outs, l, tlog, couts, ss);
+        FHS_LAUNCH((k_ntt_fwd_from_dbl_sp<LOGN, 3>), dim3(l, count), dim3(ntt_threads<LOGN - 3>()), 0, st, T,
+                   coef, outs, l, tlog, couts, ss);
 }
 // dense limbs of a compact plaintext (fhs_host.hip pt_dense): d[i N + e] = dc[i (N >> tl) + (e >> tl)]
 __global__ void k_expand_compact(const u64* __restrict__ dc, u64* __restrict__ d, int l, int N, int tl) {
@@ -3058,14 +3117,14 @@ __global__ void k_expand_compact(const u64* __restrict__ dc, u64* __restrict__ d
 }
 hipError_t launch_expand_compact(const u64* dc, u64* d, int l, int N, int tl, hipStream_t st) {
     if (tl < 1 || tl > kEncSparseMaxLog || l < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_expand_compact, dim3(eltwise_grid((size_t)l * N)), dim3(256), 0, st, dc, d, l, N, tl);
+    FHS_LAUNCH(k_expand_compact, dim3(eltwise_grid((size_t)l * N)), dim3(256), 0, st, dc, d, l, N, tl);
     return hipGetLastError();
 }
 int encode_sparse_max_log(int logN) { return std::max(0, std::min(kEncSparseMaxLog, logN - kEncSparseMinLogM)); }
 hipError_t launch_enc_period(const double* vals, int count, size_t n, size_t stride, bool is_real, int smax,
                              unsigned char* tlog, hipStream_t st) {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_enc_period, dim3(count), dim3(256), 0, st, vals, n, stride, is_real ? 1 : 0, smax, tlog);
+    FHS_LAUNCH(k_enc_period, dim3(count), dim3(256), 0, st, vals, n, stride, is_real ? 1 : 0, smax, tlog);
     return hipGetLastError();
 }
 
@@ -3074,8 +3133,8 @@ hipError_t launch_encode_coef(const DevTables& T, const double* vals, int count,
     if (count <= 0) return hipSuccess;
     FHS_DISPATCH_LOGN(T.logN, {
         constexpr int TH = ((1 << LOGN) / 16) < 1024 ? ((1 << LOGN) / 16) : 1024;
-        hipLaunchKernelGGL((k_encode<LOGN>), dim3(count), dim3(TH), 0, st, T, vals, n, stride, is_real ? 1 : 0, scale,
-                           static_cast<u64* const*>(nullptr), 0, coef, tlog, 0);
+        FHS_LAUNCH((k_encode<LOGN>), dim3(count), dim3(TH), 0, st, T, vals, n, stride, is_real ? 1 : 0, scale,
+                   static_cast<u64* const*>(nullptr), 0, coef, tlog, 0);
     });
     return hipGetLastError();
 }
@@ -3087,14 +3146,14 @@ hipError_t launch_encode(const DevTables& T, const double* vals, int count, size
     if (!couts_dev) ss = 0;
     FHS_DISPATCH_LOGN(T.logN, {
         constexpr int TH = ((1 << LOGN) / 16) < 1024 ? ((1 << LOGN) / 16) : 1024;
-        hipLaunchKernelGGL((k_encode<LOGN>), dim3(count), dim3(TH), 0, st, T, vals, n, stride, is_real ? 1 : 0, scale,
-                           outs_dev, l, coef_scratch, tlog, coef_scratch ? 1 : 0);
+        FHS_LAUNCH((k_encode<LOGN>), dim3(count), dim3(TH), 0, st, T, vals, n, stride, is_real ? 1 : 0, scale,
+                   outs_dev, l, coef_scratch, tlog, coef_scratch ? 1 : 0);
         if (coef_scratch) {
-            hipLaunchKernelGGL((k_ntt_fwd_from_dbl<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T,
-                               static_cast<const double*>(coef_scratch), outs_dev, l, tlog);
+            FHS_LAUNCH((k_ntt_fwd_from_dbl<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T,
+                       static_cast<const double*>(coef_scratch), outs_dev, l, tlog);
             if (tlog) launch_ntt_fwd_sparse<LOGN>(T, coef_scratch, outs_dev, l, count, tlog, couts_dev, ss, st);
         } else {   // unfused: the spread coefficients in every limb, the N-point NTT in place
-            hipLaunchKernelGGL((k_ntt_fwd_ptrs<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T, outs_dev, l);
+            FHS_LAUNCH((k_ntt_fwd_ptrs<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T, outs_dev, l);
         }
     });
     return hipGetLastError();
@@ -3128,14 +3187,8 @@ __global__ void k_diag_gather(const double* __restrict__ M1, const double* __res
 hipError_t launch_diag_gather(const double* M1, const double* M2, int D, int G, int n, int k0, int rows, int trans,
                               double* out, hipStream_t st) {
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_diag_gather, dim3(eltwise_grid((size_t)rows * n)), dim3(256), 0, st, M1, M2, D, G, n, k0,
-                       rows, trans, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_encode_reduce(const DevTables& T, const double* coef, int count, u64* out, int l, hipStream_t st) {
-    hipLaunchKernelGGL(k_encode_reduce, dim3(eltwise_grid((size_t)count * l * T.N)), dim3(256), 0, st, T, coef, count,
-                       out, l);
+    FHS_LAUNCH(k_diag_gather, dim3(eltwise_grid((size_t)rows * n)), dim3(256), 0, st, M1, M2, D, G, n, k0,
+               rows, trans, out);
     return hipGetLastError();
 }
 
@@ -3235,15 +3288,15 @@ __global__ void k_crt_compose_jobs(const CrtJob* __restrict__ jobs, int N) {
 hipError_t launch_crt_compose_jobs(const CrtJob* jobs_dev, int count, int max_nx, int N, hipStream_t st) {
     if (count <= 0) return hipSuccess;
     const int rows = max_nx > 0 ? (max_nx + kCrtCheckPer - 1) / kCrtCheckPer : 1;
-    hipLaunchKernelGGL(k_crt_compose_jobs, dim3((N + 255) / 256, rows, count), dim3(256), 0, st, jobs_dev, N);
+    FHS_LAUNCH(k_crt_compose_jobs, dim3((N + 255) / 256, rows, count), dim3(256), 0, st, jobs_dev, N);
     return hipGetLastError();
 }
 // the single composition is unchecked: no further limbs (nx = 0), so the kernel reads neither tables nor flag
 hipError_t launch_crt_compose(const CrtConsts& K, const u64* limbs, double* out, int N, hipStream_t st) {
     if (K.l < 1 || K.l > kCrtMaxL || K.W != K.l + 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_crt_compose, dim3((N + 255) / 256, 1), dim3(256), 0, st, K, limbs, out, N,
-                       static_cast<const u64*>(nullptr), 0, static_cast<const u64*>(nullptr),
-                       static_cast<unsigned*>(nullptr));
+    FHS_LAUNCH(k_crt_compose, dim3((N + 255) / 256, 1), dim3(256), 0, st, K, limbs, out, N,
+               static_cast<const u64*>(nullptr), 0, static_cast<const u64*>(nullptr),
+               static_cast<unsigned*>(nullptr));
     return hipGetLastError();
 }
 
@@ -3269,8 +3322,8 @@ __global__ void k_scalar(DevTables T, int op, const u64* __restrict__ a, u64* __
 hipError_t launch_scalar(const DevTables& T, int op, const u64* a, u64* out, int ncomp, int l, const ScalarConsts& K,
                          hipStream_t st) {
     if (l > kMaxScalarLimbs) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scalar, dim3(eltwise_grid((size_t)ncomp * l * T.N)), dim3(256), 0, st, T, op, a, out, ncomp, l,
-                       K);
+    FHS_LAUNCH(k_scalar, dim3(eltwise_grid((size_t)ncomp * l * T.N)), dim3(256), 0, st, T, op, a, out, ncomp, l,
+               K);
     return hipGetLastError();
 }
 
@@ -3303,8 +3356,8 @@ hipError_t launch_mod_raise(const DevTables& T, const u64* in, int l, u64* out, 
     if (e != hipSuccess) return e;
     e = launch_ntt_inv(T, scratch, 1, 1, ncomp, N, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_mod_raise_lift, dim3(eltwise_grid((size_t)ncomp * T.L0 * N)), dim3(256), 0, st, T, scratch, out,
-                       ncomp);
+    FHS_LAUNCH(k_mod_raise_lift, dim3(eltwise_grid((size_t)ncomp * T.L0 * N)), dim3(256), 0, st, T, scratch, out,
+               ncomp);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_ntt_fwd(T, out, T.L0, T.L0, ncomp, (size_t)T.L0 * N, st);
@@ -3334,12 +3387,12 @@ __global__ void k_reduce_i128(DevTables T, const int64_t* hi, const u64* lo, int
 hipError_t launch_encode_int128(const DevTables& T, const int64_t* hi, const u64* lo, int count, u64* const* outs_dev,
                                 int l, hipStream_t st) {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_reduce_i128, dim3(eltwise_grid((size_t)count * l * T.N)), dim3(256), 0, st, T, hi, lo, count,
-                       outs_dev, l);
+    FHS_LAUNCH(k_reduce_i128, dim3(eltwise_grid((size_t)count * l * T.N)), dim3(256), 0, st, T, hi, lo, count,
+               outs_dev, l);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     FHS_DISPATCH_LOGN(T.logN, {
-        hipLaunchKernelGGL((k_ntt_fwd_ptrs<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T, outs_dev, l);
+        FHS_LAUNCH((k_ntt_fwd_ptrs<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T, outs_dev, l);
     });
     return hipGetLastError();
 }

@@ -190,6 +190,7 @@ _SIGS = {
     "fhs_staging_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fhs_debug_fail_next_flushes": (C.c_int, [_vp, C.c_int]),
     "fhs_debug_fail_alloc": (C.c_int, [_vp, C.c_int, _ip]),
+    "fhs_debug_launch_ledger": (C.c_int, [C.c_int, C.c_char_p, _u64, _u64p]),
 }
 # Fork-only symbols the reference probes with try/except AttributeError (bg:449-461, 382-391): if
 # the library lacks one (an older build, or FHESPEAR_DISABLE_SYMBOLS for tests), the Python names
@@ -1174,6 +1175,26 @@ def debug_fail_alloc(ctx, nth):
     was = C.c_int()
     _check(_lib.fhs_debug_fail_alloc(ctx._h, int(nth), C.byref(was)), "debug_fail_alloc")
     return bool(was.value)
+
+
+def debug_launch_ledger(op="read"):
+    """Testing hook, one ledger per process (fhs_debug_launch_ledger): "arm" clears the ledger and starts recording
+    which kernels the library launches, "disarm" stops recording, "read" returns the recorded kernels as a sorted
+    list of names with their template arguments ("k_modup_h<12, 3, true>")."""
+    ops = {"arm": 0, "disarm": 1, "read": 2}
+    if op not in ops:
+        raise ValueError(f"debug_launch_ledger: op must be one of {sorted(ops)}")
+    if op != "read":
+        _check(_lib.fhs_debug_launch_ledger(ops[op], None, 0, None), "debug_launch_ledger")
+        return None
+    need = _u64()
+    _lib.fhs_debug_launch_ledger(2, None, 0, C.byref(need))   # a short buffer: only the size is reported
+    while True:
+        buf = C.create_string_buffer(int(need.value))
+        if _lib.fhs_debug_launch_ledger(2, buf, len(buf), C.byref(need)) == 0:
+            return buf.value.decode().splitlines()
+        if int(need.value) <= len(buf):
+            _check(1, "debug_launch_ledger")
 
 
 def staging_stats(ctx):

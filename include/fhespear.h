@@ -62,6 +62,18 @@ fhs_status fhs_debug_fail_next_flushes(fhs_context* ctx, int count);
  * hipMalloc; nth < 0 disarms it.  *was_armed (may be NULL) receives whether an arming was still pending.  Launches
  * nothing and touches no device state: every failure path can be walked without exhausting HBM. */
 fhs_status fhs_debug_fail_alloc(fhs_context* ctx, int nth, int* was_armed);
+/* Testing hook (extension, replaces no pb symbol): the launch ledger, one per process.  Every kernel launch of the
+ * library passes one macro; while the ledger is armed that macro records which kernel was launched (disarmed it
+ * costs one relaxed atomic load).  The tests use it to prove that each compiled kernel has an oracle-checked case.
+ *   FHS_LEDGER_ARM     clears the ledger and arms it
+ *   FHS_LEDGER_DISARM  stops recording; what was recorded stays readable
+ *   FHS_LEDGER_READ    writes the launched kernels to buf as sorted names, each followed by '\n', NUL-terminated:
+ *                      the kernel with its template arguments and nothing else ("k_modup_h<12, 3, true>").  *needed
+ *                      (may be NULL) receives the byte count including the NUL; a buffer shorter than that (or NULL)
+ *                      is FHS_ERR_INVALID with *needed still set.  An empty ledger reads as "".
+ * buf, len and needed are ignored by ARM and DISARM. */
+enum { FHS_LEDGER_ARM = 0, FHS_LEDGER_DISARM = 1, FHS_LEDGER_READ = 2 };
+fhs_status fhs_debug_launch_ledger(int op, char* buf, uint64_t len, uint64_t* needed);
 
 /* ---- parameters (pb:78-98) ---- */
 /* pb:81 create_coeff_modulus: SEAL CoeffModulus::Create (largest primes = 1 mod 2N per size) */
