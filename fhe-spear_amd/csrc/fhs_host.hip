@@ -2378,25 +2378,112 @@ extern "C" fhs_status fhs_encode_encrypt_symmetric_batch(fhs_context* c, fhs_sec
     std::vector<double> scales(count, scale);
     return encrypt_sym_core(c, sk, (int)count, l, ci, scales.data(), nullptr, coef.as<const double>(), outs);
 }
+// `count` public-key encryptions at l limbs with the counters ctr0 .. ctr0 + count - 1, which the caller has already
+// taken from the key (a failure below does not give them back: a mask stream is never used twice): of the
+// plaintexts pts[i], or (pts null) of the rounded message coefficients `coef` (count x N doubles,
+// launch_encode_coef) -- encode and encrypt fused.  The new ciphertexts share one device block (new_cts) that
+// the combine writes whole; they reach outs[0..count) only on success (outs is not touched otherwise).  Scratch:
+// per ciphertext 3 N bytes of small values and 3 l N words of their transforms, then the plaintext pointers (more
+// than one plaintext); the batch goes through it in runs of at most kPkScratchBytes.
+static constexpr size_t kPkScratchBytes = (size_t)1 << 30;
+static fhs_status encrypt_pk_core(fhs_context* c, fhs_public_key* pk, uint64_t ctr0, int count, int l, int ci,
+                                  const double* scales, const fhs_plaintext* const* pts, const double* coef,
+                                  fhs_ciphertext** outs) {
+    std::vector<fhs_ciphertext*> cts(count, nullptr);
+    BatchOutT<fhs_ciphertext> bo(cts.data(), count);
+    fhs_status s = new_cts(c, count, 2, ci, scales[0], cts);
+    if (s != FHS_OK) return s;
+    for (int i = 0; i < count; ++i) cts[i]->scale = scales[i];
+    const size_t S = (size_t)l * c->N;
+    const int run = (int)std::min<size_t>(count, std::max<size_t>(1, kPkScratchBytes / (24 * S)));
+    const size_t ub_bytes = 24 * S * run, small_bytes = (3 * (size_t)c->N * run + 7) & ~(size_t)7;
+    std::vector<const uint64_t*> ptrs(pts ? count : 0);
+    for (size_t i = 0; i < ptrs.size(); ++i) HIPCHK(pt_dense(c, pts[i], &ptrs[i]), "encrypt");
+    const bool by_ptrs = ptrs.size() > 1;   // a single plaintext goes as a kernel argument
+    DevTmp tmp(c);
+    HIPCHK(tmp.alloc(ub_bytes + small_bytes + (by_ptrs ? 8 * ptrs.size() : 0)), "encrypt");
+    unsigned char* small = tmp.as<unsigned char>() + ub_bytes;
+    const fhs::u64* const* dptrs = nullptr;
+    if (by_ptrs) {
+        HIPCHK(stage_h2d(c, small + small_bytes, ptrs.data(), 8 * ptrs.size()), "encrypt");
+        dptrs = reinterpret_cast<const fhs::u64* const*>(small + small_bytes);
+    }
+    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    for (int i0 = 0; i0 < count; i0 += run) {
+        const int n = std::min(run, count - i0);
+        HIPCHK(fhs::launch_encrypt_pk_batch(c->T, pk->rng, stream_id(ST_ENC_ASYM, ctr0 + (uint64_t)i0, 0),
+                                            stream_id(0, 1, 0), cts[0]->d + (size_t)i0 * 2 * S, pk->pk,
+                                            pk->pk + (size_t)c->L0 * c->N, dptrs ? dptrs + i0 : nullptr,
+                                            ptrs.size() == 1 ? ptrs[0] : nullptr,
+                                            coef ? coef + (size_t)i0 * c->N : nullptr, n, l,
+                                            reinterpret_cast<signed char*>(small), tmp.p, c->st, tm), "encrypt");
+    }
+    for (int i = 0; i < count; ++i) outs[i] = cts[i];
+    return bo.keep(FHS_OK);
+}
 extern "C" fhs_status fhs_encrypt_asymmetric(fhs_context* c, fhs_public_key* pk, const fhs_plaintext* pt,
                                              fhs_ciphertext** out) {
     ENTER(c);
     if (!pk || !pt || !out) return fail(FHS_ERR_INVALID, "encrypt: null argument");
     const uint64_t ctr = pk->ctr++;
-    NEW_CT(ct, 2, pt->ci, pt->scale);
-    const int l = pt->l;
-    const size_t S = (size_t)l * c->N, SL = (size_t)c->L0 * c->N;
-    DevTmp tmp(c);
-    HIPCHK(tmp.alloc(24 * S), "encrypt");
-    uint64_t *u = tmp.p, *e0 = tmp.p + S, *e1 = tmp.p + 2 * S;
-    HIPCHK(sample_small_ntt(c, fhs::SAMPLE_TERNARY, pk->rng, stream_id(ST_ENC_ASYM, ctr, 0), u, l), "encrypt");
-    HIPCHK(sample_small_ntt(c, fhs::SAMPLE_CBD, pk->rng, stream_id(ST_ENC_ASYM, ctr, 1), e0, l), "encrypt");
-    HIPCHK(sample_small_ntt(c, fhs::SAMPLE_CBD, pk->rng, stream_id(ST_ENC_ASYM, ctr, 2), e1, l), "encrypt");
-    PT_DENSE(pd, pt, "encrypt");
-    HIPCHK(fhs::launch_encrypt_combine(c->T, 1, ct->d, ct->d + S, pk->pk, pk->pk + SL, u, e0, e1, pd, l, c->st),
-           "encrypt");
-    *out = ct.release();
-    return FHS_OK;
+    return encrypt_pk_core(c, pk, ctr, 1, pt->l, pt->ci, &pt->scale, &pt, nullptr, out);
+}
+extern "C" fhs_status fhs_encrypt_asymmetric_batch(fhs_context* c, fhs_public_key* pk, const fhs_plaintext* const* pts,
+                                                   int count, fhs_ciphertext** outs) {
+    ENTER(c);
+    if (!pk || !pts || !outs || count < 0) return fail(FHS_ERR_INVALID, "encrypt_batch: bad arguments");
+    for (int i = 0; i < count; ++i)
+        if (!pts[i]) return fail(FHS_ERR_INVALID, "encrypt_batch: null plaintext");
+    if (count == 0) return FHS_OK;
+    bool same = true;
+    for (int i = 1; i < count; ++i) same &= pts[i]->l == pts[0]->l && pts[i]->ci == pts[0]->ci;
+    // Built aside and handed over at the end, so a failure part-way destroys what was made and leaves outs alone.
+    // Mixed levels: one at a time; same level: chunks of kMaxBatch (grid rows and scratch bound the launch).  Either
+    // way the counters are consecutive and in order, so the ciphertexts are those of one call per plaintext.
+    std::vector<fhs_ciphertext*> made(count, nullptr);
+    BatchOutT<fhs_ciphertext> bo(made.data(), count);
+    std::vector<double> scales(count);
+    for (int i = 0; i < count; ++i) scales[i] = pts[i]->scale;
+    for (int i0 = 0; i0 < count; i0 += same ? kMaxBatch : 1) {
+        const int n = same ? std::min(kMaxBatch, count - i0) : 1;
+        const uint64_t ctr0 = pk->ctr;
+        pk->ctr += (uint64_t)n;
+        const fhs_status s = encrypt_pk_core(c, pk, ctr0, n, pts[i0]->l, pts[i0]->ci, scales.data() + i0, pts + i0,
+                                             nullptr, made.data() + i0);
+        if (s != FHS_OK) return s;
+    }
+    for (int i = 0; i < count; ++i) outs[i] = made[i];
+    return bo.keep(FHS_OK);
+}
+// Extension (the public-key client of ct_ct_search.py:54-90 in one pass): encode `count` vectors and encrypt them
+// with pk -- limb for limb fhs_encode[_real]_batch followed by fhs_encrypt_asymmetric_batch, without the
+// plaintexts: the message's rounded coefficients go into the NTT of e0 (k_ntt_fwd_msg_err).  The counters are taken
+// before anything is allocated, so a failed call has used exactly `count` of them.
+extern "C" fhs_status fhs_encode_encrypt_asymmetric_batch(fhs_context* c, fhs_public_key* pk, const double* values,
+                                                          size_t count, size_t n, int is_real, double scale, int ci,
+                                                          fhs_ciphertext** outs) {
+    ENTER(c);
+    if (!pk || !outs || (!values && count && n)) return fail(FHS_ERR_INVALID, "encode_encrypt: null argument");
+    fhs_status st = encode_checks(c, n, scale, ci);
+    if (st != FHS_OK) return st;
+    if (count == 0) return FHS_OK;
+    if (count > (size_t)kMaxBatch) return fail(FHS_ERR_INVALID, "encode_encrypt: at most 4096 vectors per call");
+    const uint64_t ctr0 = pk->ctr;
+    pk->ctr += (uint64_t)count;
+    const size_t stride = is_real ? n : 2 * n, N = c->N;
+    const int l = c->L0 + 1 - ci;
+    DevTmp dvals(c), coef(c);
+    HIPCHK(dvals.alloc(8 * count * stride), "encode_encrypt");
+    HIPCHK(coef.alloc(8 * count * N), "encode_encrypt");
+    if (stride) HIPCHK(stage_h2d(c, dvals.p, values, 8 * count * stride), "encode_encrypt");
+    {
+        DevTmp tl(c);   // periodic rows: the sparse encoding, as encode_*_batch gives them
+        HIPCHK(enc_periods(c, dvals.as<const double>(), count, n, stride, is_real != 0, tl), "encode_encrypt");
+        HIPCHK(fhs::launch_encode_coef(c->T, dvals.as<const double>(), (int)count, n, stride, is_real != 0, scale,
+                                       coef.as<double>(), c->st, tl.as<const unsigned char>()), "encode_encrypt");
+    }
+    std::vector<double> scales(count, scale);
+    return encrypt_pk_core(c, pk, ctr0, (int)count, l, ci, scales.data(), nullptr, coef.as<const double>(), outs);
 }
 extern "C" fhs_status fhs_decrypt(fhs_context* c, fhs_secret_key* sk, const fhs_ciphertext* ct, fhs_plaintext** out) {
     ENTER(c);

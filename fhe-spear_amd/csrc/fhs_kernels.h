@@ -106,7 +106,8 @@ hipError_t launch_seal_corr(const DevTables& T, const u64* key, const u64* akey,
 
 // Optional per-kernel event timer (bench.py): rec(ctx, id, begin, stream) is called around launches.
 enum KernelId { KID_BSGS_INNER = 0, KID_MODUP = 1, KID_KS_IP = 2, KID_MODDOWN = 3, KID_KS_INTT = 4, KID_SPECIAL_INTT = 5,
-                KID_GIANT_SUM = 6, KID_GIANT_FINAL = 7, KID_RESCALE = 8, KID_DOT_TENSOR = 9, KID_COUNT = 10 };
+                KID_GIANT_SUM = 6, KID_GIANT_FINAL = 7, KID_RESCALE = 8, KID_DOT_TENSOR = 9, KID_ENCRYPT_PK = 10,
+                KID_COUNT = 11 };
 struct KTimer {
     void* ctx;
     void (*rec)(void* ctx, int id, int begin, hipStream_t st);
@@ -195,6 +196,18 @@ hipError_t launch_encrypt_sym_batch(const DevTables& T, const ::PrfKey& K, u64 s
 // encrypt fused -- the message enters the error's NTT, the same limbs as encoding then encrypting.
 hipError_t launch_encode_coef(const DevTables& T, const double* vals, int count, size_t n, size_t stride, bool is_real,
                               double scale, double* coef, hipStream_t st, const unsigned char* tlog = nullptr);
+// `count` public-key encryptions with the kernels of the symmetric batch and of the single call, each launched over
+// the whole batch (k_sample_small with three planes, k_ntt_fwd_small / k_ntt_fwd_msg_err, k_encrypt mode 1 with
+// blockIdx.y): ciphertext y at cts + y 2 l N (c0 then c1) of plaintext pts_dev[y] (count = 1: of `pt`, pts_dev null),
+// or (both null) of the rounded message coefficients coef + y N (launch_encode_coef) -- encode and encrypt fused.
+// u, e0, e1 of ciphertext y are the ternary / CBD / CBD values of streams sid + y sid_step + 0, 1, 2: the values of
+// launch_sample + launch_ntt_fwd (three times) + launch_encrypt_combine(mode 1) per ciphertext.  pk0, pk1: the key's
+// components at the top level (l <= L0 limbs read).  Scratch: small (3 x count x N bytes), ub (3 x count x l x N
+// words).  Timed as KID_ENCRYPT_PK.
+hipError_t launch_encrypt_pk_batch(const DevTables& T, const ::PrfKey& K, u64 sid, u64 sid_step, u64* cts,
+                                   const u64* pk0, const u64* pk1, const u64* const* pts_dev, const u64* pt,
+                                   const double* coef, int count, int l, signed char* small, u64* ub, hipStream_t st,
+                                   const KTimer* tm = nullptr);
 hipError_t launch_encrypt_combine(const DevTables& T, int mode, u64* c0, u64* c1, const u64* s_or_pk0, const u64* pk1,
                                   const u64* u_ntt, const u64* e0, const u64* e1, const u64* pt, int l, hipStream_t st);
 hipError_t launch_decrypt(const DevTables& T, const u64* ct, int ncomp, const u64* s, u64* out, int l, hipStream_t st);

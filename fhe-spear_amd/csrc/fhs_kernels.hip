@@ -2519,10 +2519,24 @@ hipError_t launch_switch_key_assemble(const DevTables& T, u64* b_out, const u64*
 
 // mode 0 (symmetric): c0 = e0 - c1 s + pt (c1 holds the uniform a); mode 1 (public key):
 // c0 = u pk0 + e0 + pt, c1 = u pk1 + e1.  pk limbs are at the top level (stride L0 N).
+// A batch (gridDim.y > 1, launch_encrypt_pk_batch): ciphertext y at c0 / c1 + y ct, its u, e0, e1 at + y ue, its
+// plaintext pts[y] (pts non-null; otherwise `pt`, which only a single ciphertext uses).
+struct EncBatch {
+    size_t ct, ue;
+    const u64* const* pts;
+};
 __global__ void k_encrypt(DevTables T, int mode, u64* c0, u64* c1, const u64* s_or_pk0, const u64* pk1, const u64* u,
-                          const u64* e0, const u64* e1, const u64* pt, int l) {
+                          const u64* e0, const u64* e1, const u64* pt, int l, EncBatch B) {
     const int N = T.N;
     const size_t S = (size_t)l * N;
+    if (const size_t y = blockIdx.y) {
+        c0 += y * B.ct;
+        c1 += y * B.ct;
+        u += y * B.ue;
+        e0 += y * B.ue;
+        e1 += y * B.ue;
+    }
+    if (B.pts) pt = B.pts[blockIdx.y];
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < S; idx += (size_t)gridDim.x * blockDim.x) {
         const int i = (int)(idx / N);
         const PrimeK& P = PK(T, i);
@@ -2540,9 +2554,12 @@ __global__ void k_encrypt(DevTables T, int mode, u64* c0, u64* c1, const u64* s_
 // coefficient (k_sample did it once per coefficient AND limb: the same PRF block l times), its forward NTT
 // reading those values straight into the transform, and the mask a drawn inside the combine -- three
 // launches for the whole batch, the same values as k_sample + NTT + k_encrypt per ciphertext.
-__global__ void k_sample_small(int mode, PrfKey K, u64 sid, u64 sid_step, int N, signed char* out) {
-    sid += blockIdx.y * sid_step;
-    out += (size_t)blockIdx.y * N;
+// Plane blockIdx.z of `out` (gridDim.y x N values each; one plane for the symmetric batch, three for
+// launch_encrypt_pk_batch): stream sid + y sid_step + z, in `mode` for z = 0 and `mode_z` for the planes after it.
+__global__ void k_sample_small(int mode, int mode_z, PrfKey K, u64 sid, u64 sid_step, int N, signed char* out) {
+    if (blockIdx.z) mode = mode_z;
+    sid += blockIdx.y * sid_step + blockIdx.z;
+    out += ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * N;
     for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
         u64 r, unused;
         prf128(K, sid, (uint32_t)n, r, unused);
@@ -2635,6 +2652,39 @@ __global__ void __launch_bounds__(ntt_threads<LOGN>()) k_ntt_fwd_msg_err(DevTabl
                                },
                                [&](int e, u64 v) { p[e] = v; });
 }
+// ---- batched public-key encryption (launch_encrypt_pk_batch), from the kernels the symmetric batch and the single
+// call already have, each launched over the whole batch: k_sample_small draws u, e0, e1 once per coefficient (planes
+// 0, 1, 2), k_ntt_fwd_small transforms the planes' rows (all three in one grid; with encode fused u's and e1's, and
+// k_ntt_fwd_msg_err transforms e0's rows with the message's rounded coefficients), and k_encrypt (mode 1) combines
+// ciphertext blockIdx.y.  ub: 3 x count x l x N words of scratch, the planes' transforms in the same order.
+hipError_t launch_encrypt_pk_batch(const DevTables& T, const PrfKey& K, u64 sid, u64 sid_step, u64* cts,
+                                   const u64* pk0, const u64* pk1, const u64* const* pts_dev, const u64* pt,
+                                   const double* coef, int count, int l, signed char* small, u64* ub, hipStream_t st,
+                                   const KTimer* tm) {
+    if (count <= 0) return hipSuccess;
+    const size_t S = (size_t)l * T.N, plane = (size_t)count * T.N;
+    const signed char* sm = small;
+    FHS_TMARK(tm, KID_ENCRYPT_PK, 1, st);
+    FHS_LAUNCH(k_sample_small, dim3((T.N + 255) / 256, count, 3), dim3(256), 0, st, (int)SAMPLE_TERNARY,
+               (int)SAMPLE_CBD, K, sid, sid_step, T.N, small);
+    FHS_DISPATCH_LOGN(T.logN, {
+        if (coef) {
+            FHS_LAUNCH((k_ntt_fwd_small<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T, sm, ub, l);
+            FHS_LAUNCH((k_ntt_fwd_msg_err<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T, coef,
+                       sm + plane, ub + count * S, l);
+            FHS_LAUNCH((k_ntt_fwd_small<LOGN>), dim3(l, count), dim3(ntt_threads<LOGN>()), 0, st, T,
+                       sm + 2 * plane, ub + 2 * count * S, l);
+        } else {
+            FHS_LAUNCH((k_ntt_fwd_small<LOGN>), dim3(l, 3 * count), dim3(ntt_threads<LOGN>()), 0, st, T, sm, ub, l);
+        }
+    });
+    const int g1 = eltwise_grid(S) / count, gx = g1 > 0 ? g1 : 1;
+    FHS_LAUNCH(k_encrypt, dim3(gx, count), dim3(256), 0, st, T, 1, cts, cts + S, pk0, pk1,
+               static_cast<const u64*>(ub), static_cast<const u64*>(ub + count * S),
+               static_cast<const u64*>(ub + 2 * count * S), pt, l, EncBatch{2 * S, S, pts_dev});
+    FHS_TMARK(tm, KID_ENCRYPT_PK, 0, st);
+    return hipGetLastError();
+}
 // ciphertext y of the batch: c1 = the uniform mask (k_sample SAMPLE_UNIFORM of stream sid + y sid_step),
 // c0 = e - c1 s + m (k_encrypt mode 0)
 __global__ void k_encrypt_sym(DevTables T, PrfKey K, u64 sid, u64 sid_step, u64* const* cts, const u64* s,
@@ -2661,7 +2711,7 @@ hipError_t launch_encrypt_sym_batch(const DevTables& T, const PrfKey& K, u64 sid
                                     u64* const* cts_dev, const u64* s, const u64* const* pts_dev, int count, int l,
                                     signed char* small, u64* eb, hipStream_t st, const double* coef) {
     if (count <= 0) return hipSuccess;
-    FHS_LAUNCH(k_sample_small, dim3((T.N + 255) / 256, count), dim3(256), 0, st, (int)SAMPLE_CBD, K, sid_err,
+    FHS_LAUNCH(k_sample_small, dim3((T.N + 255) / 256, count), dim3(256), 0, st, (int)SAMPLE_CBD, (int)SAMPLE_CBD, K, sid_err,
                sid_step, T.N, small);
     FHS_DISPATCH_LOGN(T.logN, {
         if (coef)
@@ -2679,7 +2729,7 @@ hipError_t launch_encrypt_sym_batch(const DevTables& T, const PrfKey& K, u64 sid
 hipError_t launch_encrypt_combine(const DevTables& T, int mode, u64* c0, u64* c1, const u64* s_or_pk0, const u64* pk1,
                                   const u64* u_ntt, const u64* e0, const u64* e1, const u64* pt, int l, hipStream_t st) {
     FHS_LAUNCH(k_encrypt, dim3(eltwise_grid((size_t)l * T.N)), dim3(256), 0, st, T, mode, c0, c1, s_or_pk0,
-               pk1, u_ntt, e0, e1, pt, l);
+               pk1, u_ntt, e0, e1, pt, l, EncBatch{0, 0, nullptr});
     return hipGetLastError();
 }
 

@@ -133,6 +133,9 @@ _SIGS = {
                                                      C.c_int, _vp]),
     "fhs_decrypt_decode_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _dblp]),
     "fhs_encrypt_asymmetric": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    "fhs_encrypt_asymmetric_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "fhs_encode_encrypt_asymmetric_batch": (C.c_int, [_vp, _vp, _dblp, C.c_size_t, C.c_size_t, C.c_int, C.c_double,
+                                                      C.c_int, _vp]),
     "fhs_decrypt": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "fhs_add": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "fhs_sub": (C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(_vp)]),
@@ -518,6 +521,37 @@ class public_key:
     def encrypt_asymmetric(self, ctx, pt):
         """pb:112-116"""
         return _ct(ctx, _lib.fhs_encrypt_asymmetric, self._h, pt._h, what="encrypt_asymmetric")
+
+    def encrypt_asymmetric_batch(self, ctx, pts):
+        """fhs_encrypt_asymmetric_batch: the same ciphertexts as encrypt_asymmetric over `pts` in order, with
+        the sampler, the NTTs and the combine each launched once over the batch."""
+        n = len(pts)
+        if n == 0:
+            return []
+        ins = (_vp * n)(*[p._h for p in pts])
+        outs = (_vp * n)()
+        _check(_lib.fhs_encrypt_asymmetric_batch(ctx._h, self._h, ins, n, outs), "encrypt_asymmetric_batch")
+        return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+
+    def encode_encrypt_batch(self, ctx, mat, scale, chain_index=1):
+        """Extension: one ciphertext per row of `mat` (real rows: encode_double_vector_batch, complex rows:
+        encode_complex_vector_batch) encrypted with this key -- the same ciphertexts as encoding then
+        encrypt_asymmetric_batch, in one pass without plaintexts (fhs_encode_encrypt_asymmetric_batch, at most
+        4096 rows per call: more rows go in consecutive calls)."""
+        cplx = np.iscomplexobj(mat)
+        m = np.ascontiguousarray(np.asarray(mat, dtype=np.complex128 if cplx else np.float64))
+        if m.ndim != 2:
+            raise ValueError("encode_encrypt_batch expects a 2-D array (count, values)")
+        count, n = m.shape
+        res = []
+        for r0 in range(0, count, 4096):
+            part = m[r0:r0 + 4096]
+            outs = (_vp * len(part))()
+            _check(_lib.fhs_encode_encrypt_asymmetric_batch(ctx._h, self._h, part.ctypes.data_as(_dblp), len(part), n,
+                                                            0 if cplx else 1, float(scale), int(chain_index), outs),
+                   "encode_encrypt_batch")
+            res += [ciphertext(ctx, _vp(outs[i])) for i in range(len(part))]
+        return res
 
 
 class relin_key:
@@ -1138,7 +1172,8 @@ class Event:
 
 
 KERNEL_IDS = {"k_bsgs_inner": 0, "k_modup": 1, "k_ks_ip": 2, "k_moddown": 3, "k_ks_intt": 4,
-              "k_ks_special_intt": 5, "k_giant_sum": 6, "k_giant_final": 7, "rescale": 8, "k_dot_tensor": 9}
+              "k_ks_special_intt": 5, "k_giant_sum": 6, "k_giant_final": 7, "rescale": 8, "k_dot_tensor": 9,
+              "encrypt_pk": 10}
 
 
 def kernel_timer_arm(ctx, names=None):

@@ -192,7 +192,24 @@ fhs_status fhs_encode_encrypt_symmetric_batch(fhs_context* ctx, fhs_secret_key* 
  * count x nslots x (re, im)) -- the doubles of fhs_decrypt + fhs_decode_batch, without the plaintexts */
 fhs_status fhs_decrypt_decode_batch(fhs_context* ctx, fhs_secret_key* sk, const fhs_ciphertext* const* cts, int count,
                                     int nslots, double* re_im_out);
+/* pb:112-116: c0 = u pk0 + e0 + m, c1 = u pk1 + e1 with the key's next encryption counter (the count = 1 case of
+ * the batch below) */
 fhs_status fhs_encrypt_asymmetric(fhs_context* ctx, fhs_public_key* pk, const fhs_plaintext* pt, fhs_ciphertext** out);
+/* `count` public-key encryptions in one pass (the client that holds only the public key: pb:112-116 once per
+ * plaintext; ct_ct_search.py:54-90 encrypts its database and its query that way): the same ciphertexts as
+ * `count` fhs_encrypt_asymmetric calls in order (each takes the key's next encryption counter).  The small
+ * polynomials u, e0, e1 are drawn once per coefficient (not once per limb), and the sampler, the three NTTs and the
+ * combine are each one launch over the whole batch instead of seven launches per ciphertext.  On failure nothing stays allocated and
+ * out_array is untouched; the counters the call had taken are not given back (a mask stream is never reused) */
+fhs_status fhs_encrypt_asymmetric_batch(fhs_context* ctx, fhs_public_key* pk, const fhs_plaintext* const* pts, int count,
+                                        fhs_ciphertext** out_array);
+/* Extension: encode `count` vectors of n values (is_real: n doubles each; else n interleaved (re, im)) at
+ * `scale` / `chain_index` and encrypt them with pk in one pass -- the same ciphertexts as
+ * fhs_encode[_real]_batch + fhs_encrypt_asymmetric_batch (no plaintext objects; count <= 4096).  Failure as
+ * above: a failed call has used `count` counters */
+fhs_status fhs_encode_encrypt_asymmetric_batch(fhs_context* ctx, fhs_public_key* pk, const double* values, size_t count,
+                                               size_t n, int is_real, double scale, int chain_index,
+                                               fhs_ciphertext** out_array);
 fhs_status fhs_decrypt(fhs_context* ctx, fhs_secret_key* sk, const fhs_ciphertext* ct, fhs_plaintext** out);
 
 /* ---- evaluator (pb:165-205); every op returns a NEW object ---- */
@@ -328,7 +345,8 @@ fhs_status fhs_event_destroy(void* ev);
 /* Per-kernel device time from HIP events recorded on the context stream around each launch.
  * Kernel ids: 0 k_bsgs_inner (ct x pt Hadamard-accumulate), 1 k_modup (ModUp + NTT), 2 k_ks_ip
  * (key inner product), 3 k_moddown, 4 k_ks_intt, 5 k_ks_special_intt, 6 k_giant_sum,
- * 7 k_giant_final, 8 rescale, 9 k_dot_tensor (ct x ct dot-product tensor sums).  arm(mask) enables
+ * 7 k_giant_final, 8 rescale, 9 k_dot_tensor (ct x ct dot-product tensor sums), 10 encrypt_pk
+ * (public-key encryption: the sampler, NTT and combine launches of a batch).  arm(mask) enables
  * ids (bit i); timer() reports kernel_id's accumulated ms / launch count and optionally resets every
  * accumulator. */
 fhs_status fhs_kernel_timer_arm(fhs_context* ctx, uint32_t mask);
