@@ -107,6 +107,9 @@ struct PendingRot {
 struct fhs_context {
     int device = 0;
     hipStream_t st = nullptr;
+    // side stream of the giant steps with its fork / join events (fhs_kernels.h KsSide): created with `st`, joined
+    // back into `st` before every launcher returns, so everything else sees one stream
+    fhs::KsSide side{};
     std::recursive_mutex mu;
     uint64_t N = 0;
     int logN = 0, L0 = 0, P = 0, K = 0, dnum = 0;
@@ -282,6 +285,7 @@ static void free_key(fhs_context* c, uint64_t* key) {
 
 static void ctx_sync(fhs_context* c) {
     hipStreamSynchronize(c->st);
+    if (c->side.st) hipStreamSynchronize(c->side.st);   // joined into st already; a failed join leaves it to this
 }
 // every cached block back to the device (the caller holds c->mu)
 static void trim_cache(fhs_context* c) {
@@ -897,6 +901,14 @@ extern "C" fhs_status fhs_context_create(uint64_t N, const uint64_t* primes, int
     c->fft_w = std::move(H.fft_w);
     c->slot_index = std::move(H.slot_index);
     HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking), "hipStreamCreate");
+    {   // the side stream's few short kernels go ahead of the long launch they run beside: without priority their
+        // large workgroups wait for the long launch's smaller ones to leave whole CUs free, i.e. for its tail
+        int prio_lo = 0, prio_hi = 0;
+        HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi), "hipDeviceGetStreamPriorityRange");
+        HIPCHK(hipStreamCreateWithPriority(&c->side.st, hipStreamNonBlocking, prio_hi), "hipStreamCreate (side)");
+    }
+    HIPCHK(hipEventCreateWithFlags(&c->side.fork, hipEventDisableTiming), "hipEventCreate (fork)");
+    HIPCHK(hipEventCreateWithFlags(&c->side.join, hipEventDisableTiming), "hipEventCreate (join)");
     {
         static std::once_flag exit_once;
         std::call_once(exit_once, [] { atexit(release_at_exit); });
@@ -974,6 +986,9 @@ static void ctx_free(fhs_context* c) {
             for (auto& pr : v) { ev_put(pr.first); ev_put(pr.second); }
         for (hipEvent_t e : c->timer_open)
             if (e) ev_put(e);
+        if (c->side.fork) hipEventDestroy(c->side.fork);
+        if (c->side.join) hipEventDestroy(c->side.join);
+        if (c->side.st) hipStreamDestroy(c->side.st);
         if (c->st) hipStreamDestroy(c->st);
     }
     delete c;
@@ -1461,6 +1476,13 @@ extern "C" fhs_status fhs_debug_fail_next_flushes(fhs_context* c, int count) {
     if (!c || count < 0) return fail(FHS_ERR_INVALID, "debug_fail_next_flushes: bad args");
     Guard g(c);
     c->debug_fail_flushes = count;
+    return FHS_OK;
+}
+extern "C" fhs_status fhs_debug_force_fork(fhs_context* c, int on, uint64_t* forked) {
+    if (!c) return fail(FHS_ERR_INVALID, "debug_force_fork: null context");
+    Guard g(c);
+    if (on >= 0) c->side.min_wg = on ? 0 : fhs::kForkMinWg;
+    if (forked) *forked = c->side.forked;
     return FHS_OK;
 }
 extern "C" fhs_status fhs_debug_fail_alloc(fhs_context* c, int nth, int* was_armed) {
@@ -2760,7 +2782,7 @@ static fhs_status bsgs_core(fhs_context* c, const fhs_ciphertext* const* baby, i
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_SUM, 16 * S, &sum), "bsgs sum");
     ht.mark("workspaces");
     HIPCHK(fhs::launch_bsgs(c->T, dbaby, dpts, G, Beff, D, l, keys.data(), akeys.data(), giant_elts, inner, sum, ws, wsb,
-                            c->items_dev, c->stager, c->st, tm, ptl),
+                            c->items_dev, c->stager, c->st, tm, ptl, &c->side),
            "bsgs");
     ht.mark("launch bsgs");
     if (!rescale) {
@@ -3013,7 +3035,7 @@ static fhs_status giant_steps_core(fhs_context* c, Src src, int k, int ci, doubl
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_SUM, 16 * S, &sum), "bsgs_giant_steps");
     const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
     HIPCHK(fhs::launch_bsgs(c->T, nullptr, nullptr, 1, B, B, l, keys.data(), akeys.data(), ge.data(), inner, sum, ws, wsb,
-                            c->items_dev, c->stager, c->st, tm),
+                            c->items_dev, c->stager, c->st, tm, 0, &c->side),
            "bsgs_giant_steps");
     NEW_CT(r, 2, ci, scale);
     HIPCHK(hipMemcpyAsync(r->d, sum, 16 * S, hipMemcpyDeviceToDevice, c->st), "bsgs_giant_steps");

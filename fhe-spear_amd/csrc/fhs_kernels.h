@@ -131,6 +131,27 @@ struct Stager {
     void* user;
     hipError_t (*h2d)(void* user, void* dst, const void* src, size_t bytes);
 };
+// Side stream of the giant steps (one per context, high priority, with its two events without timing).  The special
+// limbs' chain -- key products of the P special limbs per rotation, their INTT, the giant sum -- depends on the
+// special limbs of the extension only and is three latency-bound launches, so where ModUp of the data limbs is
+// long enough to hide it, it runs beside that launch instead of between the big kernels (launch_bsgs):
+//   st:    ModUp(t >= l) | fork | ModUp(t < l) -> k_ks_ip_sum                  | join | k_giant_final
+//   side:                       k_ks_ip(t >= l) -> special INTT -> k_giant_sum
+// No large kernel is split; if the side chain only got CUs at the big kernel's tail the schedule would be the
+// serial one.  That is what happens beside the hoisted rotations' key products (256-thread workgroups refill
+// every freed wave slot before a 512-thread INTT workgroup fits; measured), so
+// launch_keyswitch stays on one stream.
+// The launcher joins before it returns, on every path, so callers see one stream: everything enqueued on `st`
+// after the call is ordered after the side work, and events recorded on `st` bracket it.
+// A launch forks when its data-limb ModUp has at least min_wg workgroups (kForkMinWg; 0 forces the fork: testing
+// hook fhs_debug_force_fork) and runs the half-limb kernels (N >= 512).
+constexpr int kForkMinWg = 8 * 256;   // 8 workgroups per CU of the data-limb launch (MI355X: 256 CUs)
+struct KsSide {
+    hipStream_t st = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    int min_wg = kForkMinWg;
+    unsigned long long forked = 0;   // launches that took the forked form
+};
 // items_host[r].src must index uniq_host (U distinct inputs); items_dev holds >= R items + U pointers
 // SEAL convention (T.ks_seal): with `sh` non-null and every rotated item carrying its `corr`, inputs shared by
 // several items are decomposed once (hoisted, one stream synchronisation to read the zero flag); otherwise
@@ -148,7 +169,7 @@ size_t bsgs_workspace_bytes(const DevTables& T, int R, int l);
 hipError_t launch_bsgs(const DevTables& T, const u64* const* baby_dev, const u64* const* pts_dev, int G, int B, int D,
                        int l, const u64* const* keys_host, const u64* const* akeys_host, const u64* giant_elts, u64* inner,
                        u64* out, u64* workspace, size_t ws_bytes, void* items_dev, const Stager& sg, hipStream_t st,
-                       const KTimer* tm, int ptl = 0);
+                       const KTimer* tm, int ptl = 0, KsSide* side = nullptr);
 // inner[g] = sum_{b < G, gG + b < D} baby[b] (.) pts[gG + b] for g in [g0, g1) (k_bsgs_inner), inner laid out
 // [g][2][l][N].  ptl > 0: pts_dev are compact diagonals (word e >> ptl of each limb of l N >> ptl words holds dense
 // word e: the periodic plaintexts' shadow, fhs_host.hip encode_rows_dev), 59-bit chains only.

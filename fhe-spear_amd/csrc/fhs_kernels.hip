@@ -21,6 +21,7 @@ typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 #endif
 #include "fhs_ntt.h"
 #include "fhs_buffer.h"
+#include "fhs_xcdmap.h"
 
 #include <atomic>
 #include <cxxabi.h>
@@ -141,46 +142,8 @@ __device__ __forceinline__ const PrimeK& PK(const DevTables& T, int i) {
     return reinterpret_cast<const PrimeK*>(T.primes)[i];
 }
 
-// XCD-aware block decode.  Workgroups are dealt round-robin over the 8 XCDs (observed placement,
-// MI355X_MICROARCH.md "Workgroup dispatch"; speed only, never correctness), so block b runs on the
-// XCD shared by all blocks b' == b (mod 8).  Giving XCD x only the limbs t == x (mod 8) keeps that
-// XCD's L2 (4 MiB) holding ~E/8 primes' twiddle tables instead of all E (10 MiB at E = 39).
-// Grid = 8 * ceil(E/8) * M blocks; returns false for the padding blocks.
-//   t-inner: an XCD cycles its primes fastest (blocks sharing an input m = (digit, input) run together)
-//   t-outer: an XCD finishes one limb t across all m before the next (shared per-limb data stays hot)
-__host__ __device__ __forceinline__ int xcd_grid(int E, int M) { return 8 * ((E + 7) / 8) * M; }
-__device__ __forceinline__ bool xcd_tinner(int E, int M, int& t, int& m) {
-    const int b = blockIdx.x, x = b & 7, k = b >> 3, nx = (E - x + 7) >> 3;
-    if (nx <= 0 || k >= nx * M) return false;
-    t = x + 8 * (k % nx);
-    m = k / nx;
-    return true;
-}
-// quad-pair: XCD x takes the limbs t == x (mod 4) of the inputs m == x / 4 (mod 2) -- ~E/4 primes' twiddle
-// tables per XCD L2 (2.5 MiB at E = 39) and each input read by 4 XCDs instead of all 8 (t-inner as
-// xcd_tinner).  Grid = 8 * ceil(E/4) * ceil(M/2).
-__host__ __device__ __forceinline__ int xcd_grid_q(int E, int M) { return 8 * ((E + 3) / 4) * ((M + 1) / 2); }
-__device__ __forceinline__ bool xcd_quadpair(int E, int M, int& t, int& m) {
-    const int b = blockIdx.x, x = b & 7, k = b >> 3, pg = x & 3, mh = x >> 2;
-    const int nx = (E - pg + 3) >> 2, nm = (M - mh + 1) >> 1;
-    if (nx <= 0 || nm <= 0 || k >= nx * nm) return false;
-    t = pg + 4 * (k % nx);
-    m = mh + 2 * (k / nx);
-    return true;
-}
-// plain: blockIdx.x = t + E * m (t fastest)
-__device__ __forceinline__ bool plain_tm(int E, int M, int& t, int& m) {
-    t = blockIdx.x % E;
-    m = blockIdx.x / E;
-    return m < M;
-}
-__device__ __forceinline__ bool xcd_touter(int E, int M, int& t, int& m) {
-    const int b = blockIdx.x, x = b & 7, k = b >> 3, nx = (E - x + 7) >> 3;
-    if (nx <= 0 || k >= nx * M) return false;
-    t = x + 8 * (k / M);
-    m = k % M;
-    return true;
-}
+// Block index -> (limb, item) maps, XCD-aware where shared data should stay in one L2: fhs_xcdmap.h (plain functions
+// of blockIdx.x, proved by tools/debug/xcd_map_check.cpp)
 __device__ __forceinline__ int limb_prime(int b, int l_split, int L0) { return b < l_split ? b : L0 + (b - l_split); }
 
 // NTT-domain automorphism X -> X^elt: output slot e reads input slot galois_src(e)
@@ -726,7 +689,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 16) k_ks_intt(DevTables T, const
     __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, false>()];   // N <= 16384 (ks_intt_stage)
     const int tid = threadIdx.x;
     int i, u;
-    if (!plain_tm(l, U, i, u)) return;
+    if (!plain_tm(blockIdx.x, l, U, i, u)) return;
     const PrimeK& P = PK(T, i);
     const u64* src = uniq[u] + (size_t)i * N;
 #pragma unroll
@@ -751,7 +714,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 32, 4) k_ks_intt_h(DevTables T, 
     __shared__ __attribute__((aligned(16))) u64 lds[(1 << (LOGN - 1)) + (1 << (LOGN - 1)) / 16];
     const int tid = threadIdx.x;
     int i, u;
-    if (!plain_tm(l, U, i, u)) return;
+    if (!plain_tm(blockIdx.x, l, U, i, u)) return;
     const PrimeK& P = PK(T, i);
     const u64 q = P.q;
     // buffer loads / stores: per-lane offset tid in voffset, the half / row offsets in soffset
@@ -938,7 +901,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 16) k_modup(DevTables T, const u
     __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, false>()];
     const int P_ = T.P, K = T.K, E = l + P_, dn = (l + P_ - 1) / P_;
     int t, mi;
-    if (!xcd_tinner(E, dn * U, t, mi)) return;
+    if (!xcd_tinner(blockIdx.x, E, dn * U, t, mi)) return;
     const int j = mi % dn, u = mi / dn;
     const int s0 = j * P_, s1 = min(s0 + P_, l), ns = s1 - s0;
     u64* o = ext + (((size_t)u * dn + j) * E + t) * N;
@@ -1199,33 +1162,33 @@ __device__ __forceinline__ void modup_h_body(const DevTables& T, const u64* acoe
 template <int LOGN, int DP, bool B59>
 __global__ void __launch_bounds__((1 << LOGN) / 32, 4) k_modup_h(DevTables T, const u64* const* uniq,
                                                                  const u64* acoef, const unsigned char* vcnt, u64* ext,
-                                                                 int l, int U) {
+                                                                 int l, int U, ModupMap mp) {
     __shared__ __attribute__((aligned(16))) u64 lds[modup_h_lds_words<LOGN>()];
-    const int E = l + T.P, dn = (l + T.P - 1) / T.P;
     int t, mi;
-    if (!xcd_quadpair(E, dn * U, t, mi)) return;
+    if (!modup_map(mp, blockIdx.x, l, T.P, t, mi)) return;
     modup_h_body<LOGN, DP, B59>(T, acoef, vcnt, ext, l, t, mi, threadIdx.x, lds);
 }
 
-// The kernel and its grid are chosen first, the launch is written once (as in ks_moddown_stage)
+// The kernel and its grid are chosen first, the launch is written once (as in ks_moddown_stage).
+// part (fhs_xcdmap.h ModupPart): every target limb, or the special / the data limbs alone (half-limb form only)
 template <int LOGN>
 static void launch_modup(const DevTables& T, const u64* const* uniq, const u64* acoef, const unsigned char* vcnt,
-                         u64* ext, int l, int U, hipStream_t st) {
-    const int E = l + T.P, M = (l + T.P - 1) / T.P * U;
-    void (*k)(DevTables, const u64* const*, const u64*, const unsigned char*, u64*, int, int);
-    dim3 g(xcd_grid_q(E, M)), b((1 << LOGN) / 32);   // k_modup_h
+                         u64* ext, int l, int U, hipStream_t st, int part = kModupAll) {
     if constexpr (!ks_uses_half(LOGN)) {   // residues + counts (launch_centered wrote no X form: modup_xform is false)
-        k = k_modup<LOGN>;
-        g = dim3(xcd_grid(E, M));
-        b = dim3((1 << LOGN) / 16);
-    } else if (modup_xform(T, l)) {   // every digit of this level full (3 limbs), X form (launch_centered)
-        k = T.conv_b59 ? k_modup_h<LOGN, 3, true> : k_modup_h<LOGN, 3, false>;
-    } else if (T.modup_dp == 1) {   // all_b59: SEAL's 59-bit chains, compile-time lazy NTT and folded stores
-        k = T.all_b59 ? k_modup_h<LOGN, 1, true> : k_modup_h<LOGN, 1, false>;
+        const int E = l + T.P, M = (l + T.P - 1) / T.P * U;
+        FHS_LAUNCH(k_modup<LOGN>, dim3(xcd_grid(E, M)), dim3((1 << LOGN) / 16), 0, st, T, uniq, acoef, vcnt, ext, l, U);
     } else {
-        k = k_modup_h<LOGN, 0, false>;
+        void (*k)(DevTables, const u64* const*, const u64*, const unsigned char*, u64*, int, int, ModupMap);
+        if (modup_xform(T, l)) {   // every digit of this level full (3 limbs), X form (launch_centered)
+            k = T.conv_b59 ? k_modup_h<LOGN, 3, true> : k_modup_h<LOGN, 3, false>;
+        } else if (T.modup_dp == 1) {   // all_b59: SEAL's 59-bit chains, compile-time lazy NTT and folded stores
+            k = T.all_b59 ? k_modup_h<LOGN, 1, true> : k_modup_h<LOGN, 1, false>;
+        } else {
+            k = k_modup_h<LOGN, 0, false>;
+        }
+        const ModupMap mp = modup_map_build(l, T.P, U, part);
+        FHS_LAUNCH(k, dim3(mp.grid), dim3((1 << LOGN) / 32), 0, st, T, uniq, acoef, vcnt, ext, l, U, mp);
     }
-    FHS_LAUNCH(k, g, b, 0, st, T, uniq, acoef, vcnt, ext, l, U);
 }
 
 // (b2) key inner product with the automorphism applied on the fly, lazy 128-bit over digits:
@@ -1298,15 +1261,15 @@ __device__ __forceinline__ void ks_digits(const KsOps& o, const u64* seeds_g, u6
     acc3_fold(c1, a1);
 }
 __global__ void __launch_bounds__(256) k_ks_ip(DevTables T, const KsItem* items, const u64* const* uniq, const u64* ext,
-                                                u64* acc, int l, int R, int t0) {
+                                                u64* acc, int l, int R, int t0, int t1) {
     const int N = T.N, P_ = T.P, K = T.K, E = l + P_, dn = (l + P_ - 1) / P_;
     const int NB = N >> 8;
     int t, m;
-    // t0 == 0 (hoisted rotations of one input): the rotations of one limb t run together on one XCD, so
-    // their shared extension stays in its L2.  t0 > 0 (the giant steps' special limbs): every rotation has
-    // its own input, so nothing is shared and a plain map keeps all 8 XCDs busy (an XCD map over P = 3
-    // limbs would leave 5 of them idle)
-    if (!(t0 > 0 ? plain_tm(E - t0, R * NB, t, m) : xcd_touter(E - t0, R * NB, t, m))) return;
+    // t0 == 0 (hoisted rotations of one input, limbs [0, t1)): the rotations of one limb t run together on one XCD,
+    // so their shared extension stays in its L2.  t0 > 0 (the giant steps' special limbs): every rotation has its
+    // own input, so nothing is shared and a plain map keeps all 8 XCDs busy (an XCD map over P = 3 limbs would
+    // leave 5 of them idle)
+    if (!(t0 > 0 ? plain_tm(blockIdx.x, t1 - t0, R * NB, t, m) : xcd_touter(blockIdx.x, t1, R * NB, t, m))) return;
     t += t0;
     int r, nb;
     if (FHS_KSIP_HALVES && t0 == 0 && NB >= 2 && (size_t)dn * N * 8 > ((size_t)3 << 20)) {
@@ -1355,7 +1318,7 @@ __global__ void __launch_bounds__(256) k_ks_ip_sum(DevTables T, const KsItem* it
     const int N = T.N, P_ = T.P, K = T.K, E = l + P_, dn = (l + P_ - 1) / P_;
     const int NB = N >> 8;
     int t, m;
-    if (!xcd_touter(l, NB, t, m)) return;
+    if (!plain_tm(blockIdx.x, l, NB, t, m)) return;
     const int n = (m << 8) + threadIdx.x;
     const RedU RD = redu(PK(T, t));
     const u64 q = RD.q;
@@ -1427,7 +1390,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 16) k_moddown(DevTables T, const
     __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, false>()];
     const int P_ = T.P, E = l + P_;
     int i, m;
-    if (!plain_tm(l, 2 * R, i, m)) return;
+    if (!plain_tm(blockIdx.x, l, 2 * R, i, m)) return;
     const int comp = m & 1, r = m >> 1;
     const PrimeK& P = PK(T, i);
     const u64 q = P.q;
@@ -1775,21 +1738,57 @@ static void ks_modup_stage(const DevTables& T, const u64* const* uniq, int U, in
     launch_modup<LOGN>(T, uniq, b.acoef, b.vcnt, b.ext, l, U, st);
     FHS_TMARK(tm, KID_MODUP, 0, st);
 }
-// hoisted key inner product: every limb of every item -> acc [R][2][E][N]
-static void ks_ip_stage(const DevTables& T, const KsItem* it, const u64* const* uniq, int R, int l, const KsBufs& b,
-                        hipStream_t st, const KTimer* tm) {
-    FHS_TMARK(tm, KID_KS_IP, 1, st);
-    FHS_LAUNCH(k_ks_ip, dim3(xcd_grid(l + T.P, R * (T.N >> 8))), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R,
-               0);
-    FHS_TMARK(tm, KID_KS_IP, 0, st);
+// Fork / join of the key switch's side stream (fhs_kernels.h KsSide).  fork(): the side stream waits for what is
+// enqueued on `st` so far.  join(): `st` waits for what is enqueued on the side stream.  The destructor joins if
+// nothing did (an error path), so no launcher returns with side work that `st` is not ordered after; if the join
+// event itself cannot be enqueued, the side stream is drained on the host instead.
+struct SideFork {
+    KsSide* s;
+    hipStream_t st;
+    bool open = false;
+    SideFork(KsSide* s_, hipStream_t st_) : s(s_), st(st_) {}
+    SideFork(const SideFork&) = delete;
+    SideFork& operator=(const SideFork&) = delete;
+    ~SideFork() { (void)join(); }
+    hipError_t fork() {
+        hipError_t e = hipEventRecord(s->fork, st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s->st, s->fork, 0);
+        if (e != hipSuccess) return e;
+        open = true;
+        ++s->forked;
+        return hipSuccess;
+    }
+    hipError_t join() {
+        if (!open) return hipSuccess;
+        open = false;
+        hipError_t e = hipEventRecord(s->join, s->st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, s->join, 0);
+        if (e != hipSuccess) (void)hipStreamSynchronize(s->st);
+        return e;
+    }
+};
+// the forked form: a side stream exists, the half-limb kernels run (N >= 512) and the data-limb launch is long
+// enough to hide the special limbs' chain under
+static bool side_forks(const KsSide* s, int logN, long long data_wg) {
+    return s && s->st && ks_uses_half(logN) && data_wg >= s->min_wg;
 }
-// giant-step key inner product: the special limbs per rotation, the data limbs summed over the rotations
-static void giant_ip_stage(const DevTables& T, const KsItem* it, const u64* const* uniq, int R, int l, const KsBufs& b,
-                           hipStream_t st, const KTimer* tm) {
+// key inner product per item, limbs [t0, t1) -> acc [R][2][E][N]: every limb of hoisted rotations (t0 = 0, limbs
+// dealt over the XCDs) or the giant steps' special limbs alone (t0 = l, plain map)
+static void ks_ip_stage(const DevTables& T, const KsItem* it, const u64* const* uniq, int R, int l, const KsBufs& b,
+                        hipStream_t st, const KTimer* tm, int t0, int t1) {
     const int NB = T.N >> 8;
     FHS_TMARK(tm, KID_KS_IP, 1, st);
-    FHS_LAUNCH(k_ks_ip, dim3(T.P * R * NB), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R, l);
-    FHS_LAUNCH(k_ks_ip_sum, dim3(xcd_grid(l, NB)), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R);
+    FHS_LAUNCH(k_ks_ip, dim3(t0 > 0 ? plain_grid(t1 - t0, R * NB) : xcd_grid(t1, R * NB)), dim3(256), 0, st, T, it, uniq,
+               b.ext, b.acc, l, R, t0, t1);
+    FHS_TMARK(tm, KID_KS_IP, 0, st);
+}
+// giant-step key inner product of the data limbs, summed over the rotations (the special limbs, per rotation:
+// ks_ip_stage from t0 = l)
+static void giant_ip_sum_stage(const DevTables& T, const KsItem* it, const u64* const* uniq, int R, int l, const KsBufs& b,
+                               hipStream_t st, const KTimer* tm) {
+    const int NB = T.N >> 8;
+    FHS_TMARK(tm, KID_KS_IP, 1, st);
+    FHS_LAUNCH(k_ks_ip_sum, dim3(plain_grid(l, NB)), dim3(256), 0, st, T, it, uniq, b.ext, b.acc, l, R);
     FHS_TMARK(tm, KID_KS_IP, 0, st);
 }
 // special limbs of acc -> ycoef [R][2][P][N] (coefficient form)
@@ -1893,6 +1892,18 @@ hipError_t launch_seal_corr(const DevTables& T, const u64* key, const u64* akey,
     return hipGetLastError();
 }
 
+// ModUp -> key inner products -> special-limb INTT -> ModDown of R items over U decomposed inputs (acoef, counts / X
+// form in b): every path of launch_keyswitch.  One stream: beside the key products of the data limbs the special
+// limbs' INTT would only get CUs at that launch's tail (fhs_kernels.h KsSide)
+template <int LOGN>
+static hipError_t ks_product_stages(const DevTables& T, const KsItem* it, const u64* const* uq, int R, int U, int l,
+                                    const KsBufs& b, hipStream_t st, const KTimer* tm) {
+    ks_modup_stage<LOGN>(T, uq, U, l, b, st, tm);
+    ks_ip_stage(T, it, uq, R, l, b, st, tm, 0, l + T.P);
+    ks_special_intt_stage<LOGN>(T, R, l, b, st, tm);
+    return ks_moddown_stage<LOGN>(T, it, R, l, b, st, tm);
+}
+
 hipError_t launch_keyswitch(const DevTables& T, const KsItem* items_host, int R, const u64* const* uniq_host, int U,
                             int l, u64* ws, size_t ws_bytes, void* items_dev, const Stager& sg, hipStream_t st,
                             const KTimer* tm, SealHoist* sh) {
@@ -1918,12 +1929,7 @@ hipError_t launch_keyswitch(const DevTables& T, const KsItem* items_host, int R,
             return launch_keyswitch(T, items_host, R, uniq_host, U, l, ws, ws_bytes, items_dev, sg, st, tm, nullptr);
         }
         ++sh->hoisted;
-        FHS_DISPATCH_LOGN(T.logN, {
-            ks_modup_stage<LOGN>(T, uq, U, l, b, st, tm);
-            ks_ip_stage(T, it, uq, R, l, b, st, tm);
-            ks_special_intt_stage<LOGN>(T, R, l, b, st, tm);
-            e = ks_moddown_stage<LOGN>(T, it, R, l, b, st, tm);
-        });
+        FHS_DISPATCH_LOGN(T.logN, e = ks_product_stages<LOGN>(T, it, uq, R, U, l, b, st, tm));
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }
@@ -1944,10 +1950,7 @@ hipError_t launch_keyswitch(const DevTables& T, const KsItem* items_host, int R,
     const KsBufs b = ks_carve(T, ws, R, U, l);
     FHS_DISPATCH_LOGN(T.logN, {
         ks_intt_stage<LOGN>(T, uq, U, l, b, st, tm);
-        ks_modup_stage<LOGN>(T, uq, U, l, b, st, tm);
-        ks_ip_stage(T, it, uq, R, l, b, st, tm);
-        ks_special_intt_stage<LOGN>(T, R, l, b, st, tm);
-        me = ks_moddown_stage<LOGN>(T, it, R, l, b, st, tm);
+        me = ks_product_stages<LOGN>(T, it, uq, R, U, l, b, st, tm);
     });
     if (me != hipSuccess) return me;
     return hipGetLastError();
@@ -2114,9 +2117,15 @@ __global__ void __launch_bounds__(64 * WAVES) k_bsgs_inner(DevTables T, const u6
 #ifndef FHS_GSUM_ICH
 #define FHS_GSUM_ICH 4
 #endif
-__global__ void __launch_bounds__(256) k_giant_sum(DevTables T, const u64* bpart, const u64* ycoef, const u64* inner0,
-                                                   u64* base, u64* convsum, int l, int R) {
-    const int N = T.N, P_ = T.P, E = l + P_;
+// convsum only: it reads nothing but the special limbs' ycoef, so the whole special-limb chain can run beside the
+// data limbs' kernels (fhs_kernels.h KsSide); base is formed where it is used, in k_giant_final.
+// The rotation walk loads FHS_GSUM_RB rotations' values together (a serial walk paid one load latency per
+// rotation, and each of the limb chunks repeats it); rotations past R are not loaded and add 0.
+#ifndef FHS_GSUM_RB
+#define FHS_GSUM_RB 8
+#endif
+__global__ void __launch_bounds__(256) k_giant_sum(DevTables T, const u64* ycoef, u64* convsum, int l, int R) {
+    const int N = T.N, P_ = T.P;
     const int n = blockIdx.x * blockDim.x + threadIdx.x, comp = blockIdx.y;
     if (n >= N) return;
     const int i0 = blockIdx.z * FHS_GSUM_ICH, i1 = min(i0 + FHS_GSUM_ICH, l);
@@ -2125,14 +2134,24 @@ __global__ void __launch_bounds__(256) k_giant_sum(DevTables T, const u64* bpart
     u64 ylo[PMAX], yhi[PMAX];
 #pragma unroll
     for (int k = 0; k < PMAX; ++k) ylo[k] = yhi[k] = 0;
-    for (int r = 0; r < R; ++r) {
-        const u64* y = ycoef + ((size_t)r * 2 + comp) * P_ * N + n;
+    for (int r0 = 0; r0 < R; r0 += FHS_GSUM_RB) {
+        u64 v[FHS_GSUM_RB][PMAX];
 #pragma unroll
-        for (int k = 0; k < PMAX; ++k) {
-            if (k < P_) {
-                const u64 v = y[(size_t)k * N];
-                ylo[k] += v;
-                yhi[k] += ylo[k] < v;
+        for (int j = 0; j < FHS_GSUM_RB; ++j) {
+            const bool on = r0 + j < R;
+            const u64* y = ycoef + ((size_t)(on ? r0 + j : r0) * 2 + comp) * P_ * N + n;
+#pragma unroll
+            for (int k = 0; k < PMAX; ++k)
+                if (k < P_) v[j][k] = on ? y[(size_t)k * N] : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < FHS_GSUM_RB; ++j) {
+#pragma unroll
+            for (int k = 0; k < PMAX; ++k) {
+                if (k < P_) {
+                    ylo[k] += v[j][k];
+                    yhi[k] += ylo[k] < v[j][k];
+                }
             }
         }
     }
@@ -2152,25 +2171,26 @@ __global__ void __launch_bounds__(256) k_giant_sum(DevTables T, const u64* bpart
             cs.lo = submod(cs.lo, rh, q);
         }
         u64 cv = reduce128(cs.lo, cs.hi, P);
-        const size_t idx = (size_t)comp * S + (size_t)i * N + n;
-        const u64 bv = addmod(bpart[((size_t)comp * E + i) * N + n], inner0[idx], q);
-        convsum[idx] = cv;
-        base[idx] = bv;
+        convsum[(size_t)comp * S + (size_t)i * N + n] = cv;
     }
 }
+// out = base - NTT(convsum) P^-1 with base = bpart + inner_0 (bpart: k_ks_ip_sum's [2][E][N], limbs t < l)
 template <int LOGN, bool H = ntt_half<LOGN>()>
-__global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_giant_final(DevTables T, const u64* base, const u64* convsum,
-                                                                     u64* out, int l) {
+__global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_giant_final(DevTables T, const u64* bpart, const u64* inner0,
+                                                                     const u64* convsum, u64* out, int l) {
     constexpr int N = 1 << LOGN;
     __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, H>()];
     const int i = blockIdx.x, comp = blockIdx.y;
     const PrimeK& P = PK(T, i);
     const RedU RU = redu(P);
-    const size_t off = ((size_t)comp * l + i) * N;
+    const size_t off = ((size_t)comp * l + i) * N, boff = ((size_t)comp * (l + T.P) + i) * N;
     const u64 pinv = T.md_pinv[2 * i], pinv_s = T.md_pinv[2 * i + 1], q = RU.q;
     fwd_limb<LOGN, FHS_NTT_RL, H>(lds, threadIdx.x, T.tw_fwd + (size_t)i * N * 2, RU,
                                [&](int e) { return convsum[off + e]; },
-                               [&](int e, u64 v) { out[off + e] = submod(base[off + e], shoup(v, pinv, pinv_s, q), q); });
+                               [&](int e, u64 v) {
+                                   out[off + e] = submod(addmod(bpart[boff + e], inner0[off + e], q),
+                                                         shoup(v, pinv, pinv_s, q), q);
+                               });
 }
 
 // core key-switch workspace of the R giant rotations, then base | convsum (2 ciphertexts)
@@ -2377,11 +2397,12 @@ hipError_t launch_dot_tensor(const DevTables& T, const u64* const* q_dev, const 
 // them), then the giant steps: INTT + centred ModUp + NTT of
 // the B - 1 inner products (one ModUp each), key inner products with the automorphism applied on the
 // fly, special-limb INTT, the giant sum before ModDown (k_giant_sum) and one ModDown NTT per output
-// limb (k_giant_final).  One stream, serial: the limbs are those of the reference loop bg:464-485.
+// limb (k_giant_final).  The limbs are those of the reference loop bg:464-485.  Large launches run the special
+// limbs' chain on the context's side stream (fhs_kernels.h KsSide); joined before the call returns.
 hipError_t launch_bsgs(const DevTables& T, const u64* const* baby_dev, const u64* const* pts_dev, int G, int B, int D,
                        int l, const u64* const* keys_host, const u64* const* akeys_host, const u64* giant_elts, u64* inner,
                        u64* out, u64* ws, size_t ws_bytes, void* items_dev, const Stager& sg, hipStream_t st,
-                       const KTimer* tm, int ptl) {
+                       const KTimer* tm, int ptl, KsSide* side) {
     const int R = B - 1;
     const size_t N = T.N, S = (size_t)l * N;
     if (T.N % 128 || G < 1 || R > 512) return hipErrorInvalidValue;
@@ -2425,22 +2446,50 @@ hipError_t launch_bsgs(const DevTables& T, const u64* const* baby_dev, const u64
         he = seal_permute(T, seal_orig.data(), R, l, seal_perm, st);
         if (he != hipSuccess) return he;
     }
-    u64* base = ws + keyswitch_workspace_bytes(T, R, R, l) / 8;
-    u64* convsum = base + 2 * S;
+    // convsum [2][l][N], in the second half of the two ciphertexts' worth of words after the key-switch workspace
+    u64* convsum = ws + keyswitch_workspace_bytes(T, R, R, l) / 8 + 2 * S;
+    hipError_t ge = hipSuccess;
     FHS_DISPATCH_LOGN(T.logN, {
         const KsBufs b = ks_carve(T, ws, R, R, l);
+        const int E = l + T.P, dn = (E - 1) / T.P;
+        SideFork sf(side, st);
+        // the special limbs' chain: their key products per rotation, INTT, sum of the conversions' inputs
+        auto special_chain = [&](hipStream_t cs) {
+            ks_ip_stage(T, it, uq, R, l, b, cs, tm, l, E);
+            ks_special_intt_stage<LOGN>(T, R, l, b, cs, tm);
+            FHS_TMARK(tm, KID_GIANT_SUM, 1, cs);
+            FHS_LAUNCH(k_giant_sum, dim3((T.N + 255) / 256, 2, (l + FHS_GSUM_ICH - 1) / FHS_GSUM_ICH), dim3(256), 0, cs, T,
+                       b.ycoef, convsum, l, R);
+            FHS_TMARK(tm, KID_GIANT_SUM, 0, cs);
+        };
         ks_intt_stage<LOGN>(T, uq, R, l, b, st, tm);
-        ks_modup_stage<LOGN>(T, uq, R, l, b, st, tm);
-        giant_ip_stage(T, it, uq, R, l, b, st, tm);
-        ks_special_intt_stage<LOGN>(T, R, l, b, st, tm);
-        FHS_TMARK(tm, KID_GIANT_SUM, 1, st);
-        FHS_LAUNCH(k_giant_sum, dim3((T.N + 255) / 256, 2, (l + FHS_GSUM_ICH - 1) / FHS_GSUM_ICH), dim3(256), 0,
-                   st, T, b.acc, b.ycoef, inner, base, convsum, l, R);
-        FHS_TMARK(tm, KID_GIANT_SUM, 0, st);
-        FHS_TMARK(tm, KID_GIANT_FINAL, 1, st);
-        FHS_NTT_LAUNCH(k_giant_final, l * 2, dim3(l, 2), st, T, base, convsum, out, l);
-        FHS_TMARK(tm, KID_GIANT_FINAL, 0, st);
+        if (!side_forks(side, LOGN, (long long)l * dn * R)) {
+            ks_modup_stage<LOGN>(T, uq, R, l, b, st, tm);
+            special_chain(st);
+            giant_ip_sum_stage(T, it, uq, R, l, b, st, tm);
+        } else {   // fhs_kernels.h KsSide: the special limbs of the extension first, then their chain on the side stream
+            if constexpr (ks_uses_half(LOGN)) {
+                FHS_TMARK(tm, KID_MODUP, 1, st);
+                launch_modup<LOGN>(T, uq, b.acoef, b.vcnt, b.ext, l, R, st, kModupSpecial);
+                FHS_TMARK(tm, KID_MODUP, 0, st);
+                ge = sf.fork();
+                if (ge == hipSuccess) {
+                    special_chain(side->st);
+                    FHS_TMARK(tm, KID_MODUP, 1, st);
+                    launch_modup<LOGN>(T, uq, b.acoef, b.vcnt, b.ext, l, R, st, kModupData);
+                    FHS_TMARK(tm, KID_MODUP, 0, st);
+                    giant_ip_sum_stage(T, it, uq, R, l, b, st, tm);
+                    ge = sf.join();
+                }
+            }
+        }
+        if (ge == hipSuccess) {
+            FHS_TMARK(tm, KID_GIANT_FINAL, 1, st);
+            FHS_NTT_LAUNCH(k_giant_final, l * 2, dim3(l, 2), st, T, b.acc, inner, convsum, out, l);
+            FHS_TMARK(tm, KID_GIANT_FINAL, 0, st);
+        }
     });
+    if (ge != hipSuccess) return ge;
     return hipGetLastError();
 }
 

@@ -193,6 +193,7 @@ _SIGS = {
     "fhs_staging_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "fhs_debug_fail_next_flushes": (C.c_int, [_vp, C.c_int]),
     "fhs_debug_fail_alloc": (C.c_int, [_vp, C.c_int, _ip]),
+    "fhs_debug_force_fork": (C.c_int, [_vp, C.c_int, _u64p]),
     "fhs_debug_launch_ledger": (C.c_int, [C.c_int, C.c_char_p, _u64, _u64p]),
 }
 # Fork-only symbols the reference probes with try/except AttributeError (bg:449-461, 382-391): if
@@ -1201,6 +1202,15 @@ def debug_fail_next_flushes(ctx, count=1):
     """Testing hook: the next `count` flushes of queued rotations fail as out of memory (their outputs are
     marked lost and the queue is dropped: fhs_debug_fail_next_flushes)."""
     _check(_lib.fhs_debug_fail_next_flushes(ctx._h, int(count)), "debug_fail_next_flushes")
+
+
+def debug_force_fork(ctx, on=None):
+    """Testing hook (fhs_debug_force_fork): on=True makes every giant-step launch of `ctx` at N >= 512 run its
+    special limbs' chain on the side stream whatever its size, on=False restores the size threshold, on=None
+    changes nothing.  Returns how many launches of `ctx` have taken the forked form so far."""
+    n = C.c_uint64(0)
+    _check(_lib.fhs_debug_force_fork(ctx._h, -1 if on is None else int(bool(on)), C.byref(n)), "debug_force_fork")
+    return int(n.value)
 
 
 def debug_fail_alloc(ctx, nth):

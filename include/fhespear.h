@@ -62,6 +62,11 @@ fhs_status fhs_debug_fail_next_flushes(fhs_context* ctx, int count);
  * hipMalloc; nth < 0 disarms it.  *was_armed (may be NULL) receives whether an arming was still pending.  Launches
  * nothing and touches no device state: every failure path can be walked without exhausting HBM. */
 fhs_status fhs_debug_fail_alloc(fhs_context* ctx, int nth, int* was_armed);
+/* Testing hook (extension, replaces no pb symbol): on > 0 makes every giant-step launch of `ctx` at N >= 512 take
+ * its forked form (the special limbs' chain on the context's side stream), whatever its size; on == 0 restores the
+ * size threshold; on < 0 changes nothing.  *forked (may be NULL) receives the number of launches of `ctx` that have
+ * taken the forked form so far.  Results are the same limbs either way. */
+fhs_status fhs_debug_force_fork(fhs_context* ctx, int on, uint64_t* forked);
 /* Testing hook (extension, replaces no pb symbol): the launch ledger, one per process.  Every kernel launch of the
  * library passes one macro; while the ledger is armed that macro records which kernel was launched (disarmed it
  * costs one relaxed atomic load).  The tests use it to prove that each compiled kernel has an oracle-checked case.
