@@ -2734,6 +2734,89 @@ extern "C" fhs_status fhs_rotate_many(fhs_context* c, const fhs_ciphertext* cons
     return flush(c);
 }
 
+// ============================================================================ batched rotate-and-sum
+// x_{k+1} = x_k + rotate(x_k, stride 2^k) for n ciphertexts at once (fri:71-75 per FFN column): at step k every
+// ciphertext uses the same Galois key, so a step is ONE batched key switch over all of them (R = U = n: every item
+// has its own input, nothing is hoisted) whose ModDown also adds sigma(x0) (add0), x0 (add0i) and x1 (add1) -- no
+// add launch, no single-rotation flushes.  A step cannot run in place (the automorphism's gather reads arbitrary
+// slots of x0), so the steps ping-pong between the results' block (new_cts) and one scratch block of its size,
+// starting so that the last step lands in the results; step 0 reads the inputs, which are never written.
+// Chunks of at most kMaxItems items, and of at most kInnerSumWsCap bytes of key-switch workspace: that workspace
+// (8 N (l + dn E + 2 E + 2 P) bytes per item, + 16 l N in the SEAL convention; E = l + P, dn = ceil(l / P)) is the
+// context's grow-only SCR_KS slot, held for the context's life, and 1 GiB of it already gives every stage of a step
+// thousands of workgroups (fri's ring, N = 32768, l = 9, P = 1: 31.7 MB per item, 32 items per chunk, 10240
+// workgroups of k_ks_ip).  Chunks are independent: each runs all its steps over its own slices of the two blocks.
+constexpr size_t kInnerSumWsCap = (size_t)1 << 30;
+extern "C" fhs_status fhs_inner_sum_many(fhs_context* c, const fhs_ciphertext* const* in, int n, int dim, int stride,
+                                         const fhs_galois_keys* gk, fhs_ciphertext** out_array) {
+    ENTER(c);
+    if (!in || !gk || !out_array) return fail(FHS_ERR_INVALID, "null argument");
+    std::vector<int> steps;
+    if (const char* bad = inner_sum_steps(n, dim, stride, c->N, steps)) return fail(FHS_ERR_INVALID, bad);
+    for (int i = 0; i < n; ++i) {
+        if (!in[i]) return fail(FHS_ERR_INVALID, "null argument");
+        LIVE(in[i]);
+        if (in[i]->ncomp != 2) return fail(FHS_ERR_INVALID, "inner_sum_many expects 2-component ciphertexts");
+        if (in[i]->ci != in[0]->ci) return fail(FHS_ERR_LEVEL, "inner_sum_many: inputs must share one chain index");
+    }
+    const int K = (int)steps.size(), ci = in[0]->ci, l = in[0]->l;
+    // every step's key before anything is allocated or launched
+    std::vector<const uint64_t*> keys(K), akeys(K);
+    std::vector<uint64_t> elts(K);
+    for (int k = 0; k < K; ++k) {
+        elts[k] = fhs_galois_elt_from_step(steps[k], c->N);
+        auto it = gk->keys.find(elts[k]);
+        if (it == gk->keys.end()) return fail(FHS_ERR_KEY, "galois key for this rotation step is not present");
+        keys[k] = it->second;
+        akeys[k] = key_akey(c, it->second);
+    }
+    const size_t S = (size_t)l * c->N, per = 2 * S;
+    // chunks of equal size (within one) under both bounds
+    const size_t item_ws = fhs::keyswitch_workspace_bytes(c->T, 1, 1, l);
+    const int rmax = (int)std::max<size_t>(1, std::min<size_t>(fhs_context::kMaxItems, kInnerSumWsCap / item_ws));
+    const int nchunks = (n + rmax - 1) / rmax, rchunk = (n + nchunks - 1) / nchunks;
+    // every allocation before the first launch; the outputs are the caller's only on success
+    uint64_t* ws = nullptr;
+    const size_t wsb = K ? fhs::keyswitch_workspace_bytes(c->T, rchunk, rchunk, l) : 0;
+    if (K) HIPCHK(scratch(c, fhs_context::SCR_KS, wsb, &ws), "key-switch workspace");
+    DevTmp pong(c);
+    if (K >= 2) HIPCHK(pong.alloc(8 * (size_t)n * per), "inner_sum_many");
+    std::vector<fhs_ciphertext*> held((size_t)n), cts;
+    BatchOutT<fhs_ciphertext> bo(held.data(), (size_t)n);   // out_array stays untouched unless the call succeeds
+    fhs_status s = new_cts(c, n, 2, ci, in[0]->scale, cts);
+    if (s != FHS_OK) return s;
+    std::copy(cts.begin(), cts.end(), held.begin());
+    for (int i = 0; i < n; ++i) cts[i]->scale = in[i]->scale;
+    uint64_t* const res = cts[0]->d;   // [n][2][l][N]: one block (new_cts), or the single ciphertext
+    if (K == 0) {
+        for (int i = 0; i < n; ++i)
+            HIPCHK(hipMemcpyAsync(res + (size_t)i * per, in[i]->d, 8 * per, hipMemcpyDeviceToDevice, c->st), "inner_sum_many");
+    }
+    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    std::vector<KsItem> items;
+    std::vector<const uint64_t*> uniq;
+    for (int i0 = 0; K && i0 < n; i0 += rchunk) {
+        const int R = std::min(rchunk, n - i0);
+        items.assign(R, KsItem{});
+        uniq.resize(R);
+        for (int k = 0; k < K; ++k) {
+            // step k writes the results' block when an even number of steps follows it
+            uint64_t* dst = (K - 1 - k) % 2 == 0 ? res : pong.p;
+            const uint64_t* src = k == 0 ? nullptr : ((K - k) % 2 == 0 ? res : pong.p);
+            for (int r = 0; r < R; ++r) {
+                const uint64_t* x = src ? src + (size_t)(i0 + r) * per : in[i0 + r]->d;
+                uint64_t* o = dst + (size_t)(i0 + r) * per;
+                items[r] = KsItem{x + S, x, x + S, keys[k], o, o + S, elts[k], (uint64_t)r, akeys[k], nullptr, x};
+                uniq[r] = x + S;
+            }
+            HIPCHK(fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), R, l,
+                                         ws, wsb, c->items_dev, c->stager, c->st, tm), "key-switch");
+        }
+    }
+    std::copy(cts.begin(), cts.end(), out_array);
+    return bo.keep(FHS_OK);
+}
+
 // ============================================================================ fused BSGS
 // giant_elts: null = 5^(g G) (the matvec, bg:478-483); else B Galois elements, giant_elts[0] = 1.
 // rescale = false leaves the sum at the product scale (last SlotToCoeff group of the bootstrap).

@@ -68,7 +68,7 @@ static_assert(FHS_NTT_HALF_MIN >= 9, "N = 256 runs the full-limb kernels only");
 // 3-limb digits on the half-limb kernel's DP = 3 instantiation
 inline bool modup_xform(const DevTables& T, int l) { return T.modup_dp == 3 && l % 3 == 0 && ks_uses_half(T.logN); }
 
-// One key-switch of a batch: out = KS_key( galois_elt(a) ) + (galois_elt(add0), add1).
+// One key-switch of a batch: out = KS_key( galois_elt(a) ) + (galois_elt(add0) + add0i, add1).
 // Items whose `a` is the same polynomial share ONE ModUp (hoisting): the exact centred base
 // extension commutes with the automorphism, so the result is bit-identical to a ModUp of
 // galois_elt(a).  `src` indexes the batch's list of distinct inputs.
@@ -84,6 +84,9 @@ struct KsItem {
     const u64* akey;     // imported key: its a_j [dnum][K][N] (null: a_j regenerated from the seeds)
     const u64* corr;     // SEAL convention, hoisted: the item's correction [2][l+P][N] (launch_seal_corr),
                          // added to the key inner product before ModDown; null otherwise
+    const u64* add0i;    // added to output comp 0 as it stands (identity, after the add0 term): the x0 of a
+                         // rotate-and-sum step x + rotate(x) (fhs_inner_sum_many).  Honoured by ModDown only
+                         // (k_moddown, k_moddown_h); null everywhere else
 };
 
 // SEAL-convention hoisting (round 5).  SEAL lifts each data limb of the *automorphed* ciphertext without

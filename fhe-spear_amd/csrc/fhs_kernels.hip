@@ -1399,7 +1399,13 @@ __global__ void __launch_bounds__((1 << LOGN) / 16) k_moddown(DevTables T, const
     const u64 halfq = T.ks_seal ? T.md_pinv[3 * T.L0 + i] : 0;   // SEAL rounding: - floor(p/2) mod q_i
     const u64 pinv = T.md_pinv[2 * i], pinv_s = T.md_pinv[2 * i + 1];
     const u64* add = comp == 0 ? it.add0 : it.add1;
-    const u64 aelt = comp == 0 ? it.elt : 1;
+    const u64* addi = comp == 0 ? it.add0i : nullptr;   // identity add of comp 0 (a rotate-and-sum step's x0)
+    u64 aelt = comp == 0 ? it.elt : 1;
+    if (!add && addi) {   // alone it is an add through the identity element, as add1
+        add = addi;
+        addi = nullptr;
+        aelt = 1;
+    }
     u64* o = (comp == 0 ? it.out0 : it.out1) + (size_t)i * N;
     const u64* ac = acc + (((size_t)r * 2 + comp) * E + i) * N;
     fwd_limb<LOGN, FHS_NTT_RL, false>(
@@ -1412,6 +1418,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 16) k_moddown(DevTables T, const
         [&](int e, u64 v) {
             u64 res = shoup(submod(ac[e], v, q), pinv, pinv_s, q);
             if (add) res = addmod(res, add[(size_t)i * N + galois_src(e, aelt, LOGN)], q);
+            if (addi) res = addmod(res, addi[(size_t)i * N + e], q);
             o[e] = res;
         });
 }
@@ -1542,7 +1549,13 @@ __global__ void __launch_bounds__((1 << LOGN) / 32, 4) k_moddown_h(DevTables T, 
     }
     const u64 pinv = T.md_pinv[2 * i], pinv_s = T.md_pinv[2 * i + 1];
     const u64* add = comp == 0 ? it.add0 : it.add1;
-    const u64 aelt = comp == 0 ? it.elt : 1;
+    const u64* addi = comp == 0 ? it.add0i : nullptr;   // identity add of comp 0 (a rotate-and-sum step's x0)
+    u64 aelt = comp == 0 ? it.elt : 1;
+    if (!add && addi) {   // alone it is an add through the identity element, as add1
+        add = addi;
+        addi = nullptr;
+        aelt = 1;
+    }
     u64* o = (comp == 0 ? it.out0 : it.out1) + (size_t)i * N;
     const u64* ac = acc + (((size_t)r * 2 + comp) * E + i) * N;
 #pragma unroll 1
@@ -1571,13 +1584,17 @@ __global__ void __launch_bounds__((1 << LOGN) / 32, 4) k_moddown_h(DevTables T, 
             // so the exponent (2 rev(e) + 1) elt mod 2N is a per-thread base plus a wave-uniform term
             const unsigned rt = __brev((unsigned)tb) >> (32 - LOGN);
             const u64 ebase = ((2 * (u64)rt + 1) * aelt) & (2 * (u64)N - 1);
+            // the identity add (wave-uniform choice): its loads go out with the batch's, at the output's own slot
+            const bool ident = addi != nullptr;
+            const __amdgpu_buffer_rsrc_t rai = brsrc((ident ? addi : add) + (size_t)i * N, N * 8);
 #pragma unroll
             for (int c0 = 0; c0 < 16; c0 += 4) {
-                u64 av[4], dv[4];
+                u64 av[4], dv[4], iv[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int eo = h * NH + eoff(c0 + k);
                     av[k] = bload64(rac, tb * 8, eo * 8);
+                    iv[k] = ident ? bload64(rai, tb * 8, eo * 8) : 0;
                     const u64 ec = (2 * (u64)(__brev((unsigned)eo) >> (32 - LOGN)) * aelt) & (2 * (u64)N - 1);
                     const u64 e2 = (ebase + ec) & (2 * (u64)N - 1);
                     const int src = (int)(__brev((unsigned)((e2 - 1) >> 1)) >> (32 - LOGN));
@@ -1589,7 +1606,9 @@ __global__ void __launch_bounds__((1 << LOGN) / 32, 4) k_moddown_h(DevTables T, 
                     // (any 64-bit input) -- no run-time lazy choice per element, no canonicalisation
                     const u64 x = lds[lidx(c0 + k)];
                     const u64 dif = B59 ? av[k] + q2 - fold59(x, RU.d) : submod(av[k], fwd_canon(x, RU), q);
-                    bstore64(addmod(shoup(dif, pinv, pinv_s, q), dv[k], q), ro, tb * 8, (h * NH + eoff(c0 + k)) * 8);
+                    u64 res = addmod(shoup(dif, pinv, pinv_s, q), dv[k], q);
+                    if (ident) res = addmod(res, iv[k], q);
+                    bstore64(res, ro, tb * 8, (h * NH + eoff(c0 + k)) * 8);
                 }
             }
         } else {
@@ -1653,7 +1672,7 @@ static void seal_rewrite(const DevTables& T, KsItem* items, int R, const u64** u
             u64* pc = perm + (size_t)r * 2 * S;
             it.a = pc + S;
             if (it.add0) it.add0 = pc;
-            it.elt = 1;
+            it.elt = 1;   // add0i is an identity add: it keeps pointing at the un-permuted input
         }
         it.corr = nullptr;   // the automorphed input is decomposed itself: nothing to correct
         uniq[r] = it.a;

@@ -1,5 +1,6 @@
 // fhs_tables.h -- host-only derivation of a context's parameter tables: the host number theory, the
-// coefficient-modulus search, argument validation for fhs_context_create, every table DevTables points
+// coefficient-modulus search, argument validation for fhs_context_create and fhs_inner_sum_many (with its step
+// list: tools/debug/inner_sum_check.cpp), every table DevTables points
 // to (as std::vectors, HostTables) and the constants of the decoder's CRT composition.  No HIP runtime
 // call: fhs_host.hip uploads what build_host_tables returns, and tools/debug/tables_check.cpp checks the
 // same tables with plain g++ (through tools/debug/shim) under the host sanitizers.
@@ -258,6 +259,27 @@ static const char* context_params_error(uint64_t N, const uint64_t* primes, int 
     }
     for (int i = 0; galois_elts && i < n_elts; ++i)
         if ((galois_elts[i] & 1) == 0 || galois_elts[i] >= 2 * N) return "context_create: invalid galois element";
+    return nullptr;
+}
+
+// The rotation steps of fhs_inner_sum_many over a ring of N coefficients -- the reference loop's
+// (step = 1; while step < dim: rotate by stride * step; step *= 2), so a dim that is no power of two takes the steps
+// below it -- into `steps` (cleared first): the message of the first argument that is wrong, or null.  dim = 1 gives
+// no step.  The largest step must be a rotation fhs_rotate accepts (< N/2 slots).
+static const char* inner_sum_steps(int n, int dim, int stride, uint64_t N, std::vector<int>& steps) {
+    steps.clear();
+    if (n < 1) return "inner_sum_many: n >= 1";
+    if (dim < 1) return "inner_sum_many: dim >= 1";
+    if (stride < 1) return "inner_sum_many: stride >= 1";
+    const uint64_t slots = N / 2;
+    for (uint64_t s = 1; s < (uint64_t)dim; s <<= 1) {
+        const uint64_t step = (uint64_t)stride * s;   // < 2^31 * 2^31
+        if (step >= slots) {
+            steps.clear();
+            return "inner_sum_many: the largest step, stride * 2^(K-1), must be < slot count";
+        }
+        steps.push_back((int)step);
+    }
     return nullptr;
 }
 

@@ -153,6 +153,7 @@ _SIGS = {
     "fhs_rotate": (C.c_int, [_vp, _vp, C.c_int, _vp, C.POINTER(_vp)]),
     "fhs_apply_galois": (C.c_int, [_vp, _vp, _u64, _vp, C.POINTER(_vp)]),
     "fhs_rotate_many": (C.c_int, [_vp, C.POINTER(_vp), _ip, C.c_int, _vp, C.POINTER(_vp)]),
+    "fhs_inner_sum_many": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
     "fhs_bsgs_multiply_accumulate": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.c_int, _vp,
                                                C.POINTER(_vp)]),
     "fhs_offload_plaintexts": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _u64p]),
@@ -880,6 +881,34 @@ def hoisting(ctx, a, gk, steps):
     outs = (_vp * n)()
     _check(_lib.fhs_rotate_many(ctx._h, ins, st, n, gk._h, outs), "hoisting")
     return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+
+
+def inner_sum_many(ctx, cts, dim, gk, stride=1):
+    """Extension: the rotate-and-sum of the slots for every ciphertext of `cts` at once (fhs_inner_sum_many) --
+    x = add(x, rotate(x, stride * step)) for step = 1, 2, 4, ... < dim, the loop of the reference's ct_pt_dot
+    (fhe_rwkv_inference.py:71-75), limb-identical to it, with ONE batched key switch per step over all of them
+    and the adds fused into its ModDown.  dim=1 returns copies; the inputs share one chain index, their scales
+    may differ.  The results share one device block."""
+    cts = list(cts)
+    n = len(cts)
+    ins = (_vp * n)(*[c._h for c in cts])
+    outs = (_vp * n)()
+    _check(_lib.fhs_inner_sum_many(ctx._h, ins, n, int(dim), int(stride), gk._h, outs), "inner_sum_many")
+    return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+
+
+def inner_sum(ctx, ct, dim, gk, stride=1):
+    """inner_sum_many of one ciphertext: slot j of the result holds sum_{i < dim} ct[j + i * stride] (dim a power
+    of two)."""
+    return inner_sum_many(ctx, [ct], dim, gk, stride)[0]
+
+
+def ct_pt_dot_many(ctx, ct, pts, dim, gk):
+    """Extension: the reference's ct_pt_dot (fhe_rwkv_inference.py:66-76) for every plaintext of `pts` --
+    rescale_to_next(multiply_plain(ct, pt)) per column, then ONE inner_sum_many over all columns, limb-identical
+    to the per-column calls."""
+    prods = [rescale_to_next(ctx, multiply_plain(ctx, ct, p)) for p in pts]
+    return inner_sum_many(ctx, prods, dim, gk)
 
 
 def bsgs_multiply_accumulate(ctx, ct_baby, pts, G, B, D, gk):

@@ -239,6 +239,19 @@ fhs_status fhs_apply_galois(fhs_context* ctx, const fhs_ciphertext* a, uint64_t 
 /* batch of rotations of possibly different inputs: out[i] = rotate(in[i], steps[i]) */
 fhs_status fhs_rotate_many(fhs_context* ctx, const fhs_ciphertext* const* in, const int* steps, int n,
                            const fhs_galois_keys* gk, fhs_ciphertext** out);
+/* Extension (fri:71-75): out[i] = x_K, where x_0 = in[i] and x_{k+1} = x_k + rotate(x_k, stride * 2^k),
+ * for every k with 2^k < dim. Limb-identical to that loop of fhs_rotate + fhs_add per ciphertext.
+ * The batched rotate-and-sum of the slots (ct_pt_dot's tail for every FFN column at once; the server-side slot sum
+ * of a retrieval score): per step ONE key switch over all n ciphertexts, its ModDown adding x_k as well, following
+ * the context's key-switch mode.  n >= 1, dim >= 1, stride >= 1; dim = 1 copies the inputs; a dim that is no power
+ * of two takes the loop's steps (dim = 3: steps 1 and 2); the largest step must be < N/2 (else FHS_ERR_INVALID).
+ * Inputs have 2 components (else FHS_ERR_INVALID) and share one chain index (else FHS_ERR_LEVEL); scales may differ,
+ * each output keeps its input's scale and chain index.  A Galois key missing for any step is FHS_ERR_KEY, found
+ * before anything is allocated or launched.  On failure nothing stays allocated and out_array is untouched.
+ * Lifetime: the n results share one device block (as the plaintexts of a batch creator do), returned to the cache
+ * when the LAST of them is destroyed.  The inputs are not written and may be destroyed as soon as the call returns. */
+fhs_status fhs_inner_sum_many(fhs_context* ctx, const fhs_ciphertext* const* in, int n, int dim, int stride,
+                              const fhs_galois_keys* gk, fhs_ciphertext** out_array);
 
 /* ---- fused BSGS (fork-only pyPhantom symbols, bg:459, bg:515) ----
  * Semantics identical, limb for limb, to the loop scripts/bootstrap_generation.py:464-485:
