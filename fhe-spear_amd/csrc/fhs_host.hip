@@ -179,7 +179,7 @@ struct fhs_context {
     enum { SCR_KS, SCR_BSGS_INNER, SCR_BSGS_WS, SCR_BSGS_SUM, SCR_RESCALE, SCR_ENC_PTRS, SCR_COUNT };
     uint64_t* scr[SCR_COUNT] = {};
     size_t scr_bytes[SCR_COUNT] = {};
-    static constexpr int kMaxItems = 512;
+    static constexpr int kMaxItems = kKsMaxItems;
     static constexpr int kMaxPtrs = 1 << 16;
 };
 
@@ -2592,7 +2592,8 @@ extern "C" fhs_status fhs_multiply(fhs_context* c, const fhs_ciphertext* a, cons
     if (s != FHS_OK) return s;
     if (a->ncomp != 2 || b->ncomp != 2) return fail(FHS_ERR_INVALID, "multiply expects 2-component ciphertexts");
     NEW_CT(r, 3, a->ci, a->scale * b->scale);
-    HIPCHK(fhs::launch_tensor(c->T, a->d, b->d, r->d, a->l, c->st), "multiply");
+    // one pair: its pointers travel as kernel arguments, nothing is staged
+    HIPCHK(fhs::launch_tensor(c->T, nullptr, nullptr, a->d, b->d, 1, r->d, a->l, c->st), "multiply");
     *out = r.release();
     return FHS_OK;
 }
@@ -3046,6 +3047,101 @@ extern "C" fhs_status fhs_dot_product_many(fhs_context* c, const fhs_ciphertext*
         }
     }
     if (rescale) HIPCHK(fhs::launch_rescale(c->T, rk ? relin : t3, outs[0]->d, scr, ocomp * C, l, c->st, tm), "rescale");
+    return bo.keep(FHS_OK);
+}
+
+// ============================================================================ batched multiply, relinearize, rescale
+// out[i] = [rescale]([relinearize](a[i] (x) b[i])) for n pairs (fri:97-108, ct_ct_square per FFN column and
+// ct_ct_multiply per channel), limb-identical to fhs_multiply, fhs_relinearize, fhs_rescale_to_next per pair.  Per
+// chunk of R pairs: ONE tensor launch (k_tensor, the pair from the grid) into a scratch [R][3][l][N], ONE batched key
+// switch of R items (a = comp 2, add0 = comp 0, add1 = comp 1, as fhs_relinearize) into [R][2][l][N], and ONE
+// rescale launch over the chunk's components straight into the chunk's slice of the results' block (new_cts),
+// which is contiguous in exactly the layout launch_rescale writes; the last stage present writes the results.
+// Chunks (fhs_tables.h batch_chunks) are bounded by kMaxItems and by kMulManyCap bytes of scratch per chunk -- per
+// item the key-switch workspace (8 N (l + dn E + 2 E + 2 P), + 16 l N in the SEAL convention; E = l + P,
+// dn = ceil(l / P)), the tensor product (24 l N), the relinearized pair (16 l N) and the rescale's last limbs (16 N
+// or 24 N), whichever of them the call uses.
+extern "C" fhs_status fhs_multiply_relin_many(fhs_context* c, const fhs_ciphertext* const* a,
+                                              const fhs_ciphertext* const* b, int n, const fhs_relin_key* rk, int rescale,
+                                              fhs_ciphertext** out_array) {
+    ENTER(c);
+    const bool null_arg = !a || !out_array;
+    const size_t cnt = (null_arg || n < 1) ? 0 : (size_t)n * (b ? 2 : 1);
+    std::vector<int> ncomp(cnt), cis(cnt);
+    for (size_t k = 0; k < cnt; ++k) {
+        const fhs_ciphertext* x = k < (size_t)n ? a[k] : b[k - n];
+        if (!x) return fail(FHS_ERR_INVALID, "null argument");
+        LIVE(x);
+        ncomp[k] = x->ncomp;
+        cis[k] = x->ci;
+    }
+    bool level = false;
+    if (const char* bad = multiply_many_error(null_arg, n, ncomp.data(), cis.data(), cnt, c->L0, rescale, &level))
+        return fail(level ? FHS_ERR_LEVEL : FHS_ERR_INVALID, bad);
+    const int ci = a[0]->ci, l = a[0]->l, ocomp = rk ? 2 : 3;
+    const size_t S = (size_t)l * c->N;
+    // chunks of equal size (within one) under both bounds; the scratch is the largest (first) chunk's
+    const size_t item = (rk ? fhs::keyswitch_workspace_bytes(c->T, 1, 1, l) : 0) + ((rk || rescale) ? 8 * 3 * S : 0) +
+                        ((rk && rescale) ? 8 * 2 * S : 0) + (rescale ? 8ull * ocomp * c->N : 0);
+    const std::vector<std::pair<int, int>> chunks = batch_chunks(n, item, fhs_context::kMaxItems, kMulManyCap);
+    const int Rmax = chunks[0].second;
+    // every allocation before the first launch; out_array is written only on success
+    uint64_t *t3 = nullptr, *relin = nullptr, *ws = nullptr, *scr = nullptr;
+    if (rk || rescale) HIPCHK(scratch(c, fhs_context::SCR_BSGS_INNER, 8ull * Rmax * 3 * S, &t3), "multiply_relin_many");
+    if (rk && rescale) HIPCHK(scratch(c, fhs_context::SCR_BSGS_SUM, 8ull * Rmax * 2 * S, &relin), "multiply_relin_many");
+    const size_t wsb = rk ? fhs::keyswitch_workspace_bytes(c->T, Rmax, Rmax, l) : 0;
+    if (rk) HIPCHK(scratch(c, fhs_context::SCR_KS, wsb, &ws), "key-switch workspace");
+    if (rescale) HIPCHK(scratch(c, fhs_context::SCR_RESCALE, 8ull * ocomp * Rmax * c->N, &scr), "rescale");
+    std::vector<fhs_ciphertext*> held((size_t)n), cts;
+    BatchOutT<fhs_ciphertext> bo(held.data(), (size_t)n);
+    fhs_status s = new_cts(c, n, ocomp, rescale ? ci + 1 : ci, 1.0, cts);
+    if (s != FHS_OK) return s;
+    std::copy(cts.begin(), cts.end(), held.begin());
+    for (int i = 0; i < n; ++i) {
+        const double sc = a[i]->scale * (b ? b[i] : a[i])->scale;   // fhs_multiply's, then fhs_rescale_to_next's
+        cts[i]->scale = rescale ? sc / (double)c->q[l - 1] : sc;
+    }
+    uint64_t* const res = cts[0]->d;   // [n][ocomp][l or l - 1][N]: one block (new_cts), or the single ciphertext
+    const size_t per_out = (size_t)ocomp * (rescale ? l - 1 : l) * c->N;
+    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    const uint64_t* akey = rk ? key_akey(c, rk->key) : nullptr;
+    std::vector<const uint64_t*> ptrs, uniq;
+    std::vector<KsItem> items;
+    for (const auto& ch : chunks) {
+        const int i0 = ch.first, R = ch.second;
+        uint64_t* const slice = res + (size_t)i0 * per_out;
+        // each stage lands where the next one reads it: the results' slice itself when nothing follows
+        uint64_t* const tdst = (rk || rescale) ? t3 : slice;
+        if (R == 1) {
+            HIPCHK(fhs::launch_tensor(c->T, nullptr, nullptr, a[i0]->d, (b ? b[i0] : a[i0])->d, 1, tdst, l, c->st),
+                   "multiply_relin_many");
+        } else {
+            // the chunk's pointer lists, a's then b's (squares: a's alone, read as both), staged in stream order
+            ptrs.resize((size_t)R * (b ? 2 : 1));
+            for (int r = 0; r < R; ++r) {
+                ptrs[r] = a[i0 + r]->d;
+                if (b) ptrs[R + r] = b[i0 + r]->d;
+            }
+            HIPCHK(stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * ptrs.size()), "multiply_relin_many");
+            const uint64_t* const* da = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
+            HIPCHK(fhs::launch_tensor(c->T, da, b ? da + R : da, nullptr, nullptr, R, tdst, l, c->st), "multiply_relin_many");
+        }
+        if (rk) {
+            uint64_t* const kdst = rescale ? relin : slice;   // [R][2][l][N]
+            items.resize(R);
+            uniq.resize(R);
+            for (int r = 0; r < R; ++r) {
+                const uint64_t* t = t3 + (size_t)r * 3 * S;
+                uint64_t* o = kdst + (size_t)r * 2 * S;
+                items[r] = KsItem{t + 2 * S, t, t + S, rk->key, o, o + S, 1, (uint64_t)r, akey};
+                uniq[r] = t + 2 * S;
+            }
+            HIPCHK(fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), R, l,
+                                         ws, wsb, c->items_dev, c->stager, c->st, tm), "key-switch");
+        }
+        if (rescale) HIPCHK(fhs::launch_rescale(c->T, rk ? relin : t3, slice, scr, ocomp * R, l, c->st, tm), "rescale");
+    }
+    std::copy(cts.begin(), cts.end(), out_array);
     return bo.keep(FHS_OK);
 }
 

@@ -124,7 +124,11 @@ hipError_t launch_ntt_inv(const DevTables& T, u64* data, int limbs, int l_split,
                           hipStream_t st);
 hipError_t launch_eltwise(const DevTables& T, int op, const u64* a, const u64* b, u64* out, int ncomp, int l,
                           size_t a_cstride, size_t b_cstride, hipStream_t st);
-hipError_t launch_tensor(const DevTables& T, const u64* a, const u64* b, u64* out3, int l, hipStream_t st);
+// out3[r] = a[r] (x) b[r] for r < R (k_tensor, one launch), out3 laid out [r][3][l][N].  The operands of pair r are
+// a_dev[r], b_dev[r] (device pointer lists), or with a_dev null and R = 1 the pointers a, b themselves.  Operands
+// that are the same pointer take the square form (half the reads, the same limbs).
+hipError_t launch_tensor(const DevTables& T, const u64* const* a_dev, const u64* const* b_dev, const u64* a, const u64* b,
+                         int R, u64* out3, int l, hipStream_t st);
 hipError_t launch_rescale(const DevTables& T, const u64* in, u64* out, u64* scratch, int ncomp, int l,
                           hipStream_t st, const KTimer* tm = nullptr);
 // Stream-ordered host->device copy of small launch descriptors (item lists, pointer arrays).  The

@@ -493,25 +493,90 @@ hipError_t launch_eltwise(const DevTables& T, int op, const u64* a, const u64* b
     return hipGetLastError();
 }
 
-// (a0 b0, a0 b1 + a1 b0, a1 b1)  -- pb:177 multiply
-__global__ void k_tensor(DevTables T, const u64* __restrict__ a, const u64* __restrict__ b, u64* __restrict__ out,
-                         int l) {
-    const int N = T.N;
-    const size_t S = (size_t)l * N;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < S; idx += (size_t)gridDim.x * blockDim.x) {
-        const int i = (int)(idx / N);
-        const PrimeK& P = PK(T, i);
-        const u64 a0 = a[idx], a1 = a[S + idx], b0 = b[idx], b1 = b[S + idx];
-        out[idx] = mulmod(a0, b0, P);
-        u128 m = {0, 0};
-        mac128(m, a0, b1);
-        mac128(m, a1, b0);
-        out[S + idx] = reduce128(m.lo, m.hi, P);
-        out[2 * S + idx] = mulmod(a1, b1, P);
+// out[r] = (a0 b0, a0 b1 + a1 b0, a1 b1) of pair r = blockIdx.z  -- pb:177 multiply, R pairs in one launch.
+// The pair's operands are ap[r], bp[r] (device pointer lists, fhs_multiply_relin_many) or, with ap null, the
+// arguments a1, b1 themselves (fhs_multiply: one pair, nothing staged); out[r] at out + r 3 l N.  Everything that
+// selects a path -- pair, limb, list or direct, square -- comes from the grid and the arguments, so it is
+// wave-uniform: the pointers and the limb's prime are scalar loads, once per workgroup.
+// A workgroup owns 512 `vecs` coefficients of limb blockIdx.y of its pair; a thread `vecs` (1 or 2) 16-byte vectors
+// of each stream, 256 x 16 bytes apart (a wave-instruction reads 1 KiB contiguously), all requested before the
+// first product.  vecs = 2 (a batch): 4 streams x 2 x 16 bytes = 128 bytes per thread, 32 KiB per workgroup in
+// flight, which is what a CU needs outstanding to stream from HBM; 7 words move per coefficient (4 in, 3 out) and a
+// chunk of 64 pairs at fri's ring (N = 32768, l = 9) runs at HBM rate (measured).  One pair alone
+// is too few waves for that shape -- 288 workgroups, one wave per SIMD, nothing to cover a wave's load latency or its
+// ~70 64-bit multiply-adds per coefficient (measured: 8.1 us against the 6.7 us of the former 8-byte kernel) -- so
+// launch_tensor gives small grids vecs = 1: twice the waves, half the serial work in each.
+// Square (the pair's operands are the same pointer): 2 words in instead of 4, b taken from a's registers -- the same
+// products and the same 128-bit middle sum a0 a1 + a1 a0 reduced once, so the same residues as the general path.
+// The operands come from a pointer list or from either of two arguments, so the compiler cannot tell their address
+// space and would read them with flat loads: they are device memory, said so here (global_load_dwordx4).
+typedef u64 tensor_v2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ tensor_v2 tensor_ld(const u64* p) {
+    return *reinterpret_cast<const __attribute__((address_space(1))) tensor_v2*>((uintptr_t)p);
+}
+// One thread's share of a row: every load first, then the products.  SQ is a code path of its own (chosen by a uniform
+// branch in the kernel), so that no register of the second operand exists on it and nothing waits between the loads.
+template <bool SQ, int VECS>
+__device__ __forceinline__ void tensor_row(const u64* a, const u64* b, u64* o, size_t S, int e0, int N, const PrimeK& P) {
+    tensor_v2 x0[VECS], x1[VECS], y0[VECS], y1[VECS];
+#pragma unroll
+    for (int u = 0; u < VECS; ++u) {
+        const int e = e0 + u * 512;
+        if (e < N) {
+            x0[u] = tensor_ld(a + e);
+            x1[u] = tensor_ld(a + S + e);
+            if constexpr (!SQ) {
+                y0[u] = tensor_ld(b + e);
+                y1[u] = tensor_ld(b + S + e);
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < VECS; ++u) {
+        const int e = e0 + u * 512;
+        if (e < N) {
+            const tensor_v2 b0 = SQ ? x0[u] : y0[u], b1 = SQ ? x1[u] : y1[u];
+            u128 mx = {0, 0}, my = {0, 0};
+            mac128(mx, x0[u].x, b1.x);
+            mac128(mx, x1[u].x, b0.x);
+            mac128(my, x0[u].y, b1.y);
+            mac128(my, x1[u].y, b0.y);
+            *reinterpret_cast<ulonglong2*>(o + e) = make_ulonglong2(mulmod(x0[u].x, b0.x, P), mulmod(x0[u].y, b0.y, P));
+            *reinterpret_cast<ulonglong2*>(o + S + e) =
+                make_ulonglong2(reduce128(mx.lo, mx.hi, P), reduce128(my.lo, my.hi, P));
+            *reinterpret_cast<ulonglong2*>(o + 2 * S + e) =
+                make_ulonglong2(mulmod(x1[u].x, b1.x, P), mulmod(x1[u].y, b1.y, P));
+        }
     }
 }
-hipError_t launch_tensor(const DevTables& T, const u64* a, const u64* b, u64* out3, int l, hipStream_t st) {
-    FHS_LAUNCH(k_tensor, dim3(eltwise_grid((size_t)l * T.N)), dim3(256), 0, st, T, a, b, out3, l);
+__global__ void __launch_bounds__(256) k_tensor(DevTables T, const u64* const* __restrict__ ap,
+                                                const u64* const* __restrict__ bp, const u64* a1, const u64* b1,
+                                                u64* __restrict__ out, int l, int vecs) {
+    const int N = T.N;
+    const size_t S = (size_t)l * N;
+    const int i = blockIdx.y, r = blockIdx.z;
+    const u64* a = ap ? ap[r] : a1;
+    const u64* b = ap ? bp[r] : b1;
+    const PrimeK& P = PK(T, i);
+    const size_t row = (size_t)i * N;
+    const int e0 = blockIdx.x * 512 * vecs + threadIdx.x * 2;
+    u64* o = out + (size_t)r * 3 * S + row;
+    if (vecs == 2) {
+        if (a == b) tensor_row<true, 2>(a + row, a + row, o, S, e0, N, P);
+        else tensor_row<false, 2>(a + row, b + row, o, S, e0, N, P);
+    } else {
+        if (a == b) tensor_row<true, 1>(a + row, a + row, o, S, e0, N, P);
+        else tensor_row<false, 1>(a + row, b + row, o, S, e0, N, P);
+    }
+}
+hipError_t launch_tensor(const DevTables& T, const u64* const* a_dev, const u64* const* b_dev, const u64* a, const u64* b,
+                         int R, u64* out3, int l, hipStream_t st) {
+    if (R < 1 || R > 65535 || l < 1 || l > 65535 || (a_dev ? !b_dev : (R != 1 || !a || !b))) return hipErrorInvalidValue;
+    // two vectors per thread once that still leaves 8 workgroups per CU (MI355X: 256 CUs), else one
+    const size_t wg2 = (size_t)((T.N + 1023) / 1024) * l * R;
+    const int vecs = wg2 >= 8 * 256 ? 2 : 1;
+    FHS_LAUNCH(k_tensor, dim3((T.N + 512 * vecs - 1) / (512 * vecs), l, R), dim3(256), 0, st, T, a_dev, b_dev, a, b, out3, l,
+               vecs);
     return hipGetLastError();
 }
 

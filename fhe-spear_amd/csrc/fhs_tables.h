@@ -1,6 +1,7 @@
 // fhs_tables.h -- host-only derivation of a context's parameter tables: the host number theory, the
 // coefficient-modulus search, argument validation for fhs_context_create and fhs_inner_sum_many (with its step
-// list: tools/debug/inner_sum_check.cpp), every table DevTables points
+// list: tools/debug/inner_sum_check.cpp) and fhs_multiply_relin_many (with its chunk plan:
+// tools/debug/multiply_many_check.cpp), every table DevTables points
 // to (as std::vectors, HostTables) and the constants of the decoder's CRT composition.  No HIP runtime
 // call: fhs_host.hip uploads what build_host_tables returns, and tools/debug/tables_check.cpp checks the
 // same tables with plain g++ (through tools/debug/shim) under the host sanitizers.
@@ -12,6 +13,7 @@
 #include <complex>
 #include <map>
 #include <set>
+#include <utility>
 #include <vector>
 
 #include "fhs_modarith.h"
@@ -281,6 +283,55 @@ static const char* inner_sum_steps(int n, int dim, int stride, uint64_t N, std::
         steps.push_back((int)step);
     }
     return nullptr;
+}
+
+// The arguments of fhs_multiply_relin_many, from what the host layer reads off the handles: n pairs, `count`
+// operand entries (n for squares, 2 n for pairs: a's then b's) with their component counts and chain indices, the
+// context's L0 and the rescale flag.  The message of the first argument that is wrong, or null; *level is set when
+// that argument is a level error (FHS_ERR_LEVEL) rather than an invalid one.
+static const char* multiply_many_error(bool null_arg, int n, const int* ncomp, const int* ci, size_t count, int L0,
+                                       int rescale, bool* level) {
+    *level = false;
+    if (null_arg) return "null argument";
+    if (n < 1) return "multiply_relin_many: n >= 1";
+    if (!ncomp || !ci || count < (size_t)n) return "null argument";
+    for (size_t k = 0; k < count; ++k)
+        if (ncomp[k] != 2) return "multiply expects 2-component ciphertexts";
+    *level = true;
+    for (size_t k = 1; k < count; ++k)
+        if (ci[k] != ci[0]) return "multiply_relin_many: inputs must share one chain index";
+    if (ci[0] < 1 || ci[0] > L0) return "chain index out of range";
+    if (rescale && L0 + 1 - ci[0] < 2) return "rescale_to_next: no level left (end of modulus switching chain)";
+    *level = false;
+    return nullptr;
+}
+// The item buffer of a key-switch launch (fhs_context::kMaxItems) and the scratch a chunk of fhs_multiply_relin_many
+// may ask for.  That scratch -- key-switch workspace, tensor products, relinearized pairs, the rescale's last limbs
+// -- lives in the context's grow-only slots, held for its life, so the cap is what a long-lived context pays for
+// having used the entry once: 1 GiB, the cap fhs_inner_sum_many already puts on the same key-switch slot (a context
+// that ran one holds little more after the other), under 0.4 % of the MI355X's HBM.  At fri's ring (N = 32768, l = 9,
+// P = 1) an item costs 31.7 + 7.1 + 4.7 MB = 43.5 MB, so a chunk is at most 24 pairs however many columns there
+// are: 6912 workgroups of k_tensor and 7680 of k_ks_ip per launch, tens per CU -- a larger chunk would add scratch
+// but no parallelism, and a thousand columns ask for 1 GiB, not 43 GB.
+constexpr int kKsMaxItems = 512;
+constexpr size_t kMulManyCap = (size_t)1 << 30;
+// The chunks of a batch of n items whose scratch costs item_bytes each: (first item, item count) per chunk, in
+// order, covering [0, n) once.  The fewest chunks with none above max_items items or cap_bytes of scratch (a single
+// item is always allowed: it cannot be split), sized within one of each other, the larger ones first.
+static std::vector<std::pair<int, int>> batch_chunks(int n, size_t item_bytes, int max_items, size_t cap_bytes) {
+    std::vector<std::pair<int, int>> chunks;
+    if (n < 1) return chunks;
+    size_t rmax = item_bytes ? cap_bytes / item_bytes : (size_t)n;
+    if (max_items >= 1 && rmax > (size_t)max_items) rmax = (size_t)max_items;
+    if (rmax < 1) rmax = 1;
+    const size_t count = ((size_t)n + rmax - 1) / rmax, base = (size_t)n / count, rem = (size_t)n % count;
+    size_t at = 0;
+    for (size_t k = 0; k < count; ++k) {
+        const size_t r = base + (k < rem ? 1 : 0);
+        chunks.emplace_back((int)at, (int)r);
+        at += r;
+    }
+    return chunks;
 }
 
 // ============================================================================ parameter tables

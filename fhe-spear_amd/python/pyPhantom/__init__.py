@@ -163,7 +163,8 @@ _SIGS = {
     "fhs_bsgs_inner_products": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.POINTER(_vp)]),
     "fhs_dot_product_many": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _vp, C.c_int,
                                        C.POINTER(_vp)]),
-    "fhs_bsgs_giant_steps": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _u64p, _vp, C.POINTER(_vp)]),
+    "fhs_multiply_relin_many": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
+    "fhs_bsgs_giant_steps":(C.c_int, [_vp, C.POINTER(_vp), C.c_int, _u64p, _vp, C.POINTER(_vp)]),
     "fhs_bsgs_inner_products_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _vp]),
     "fhs_bsgs_giant_steps_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, _u64p, _vp, C.POINTER(_vp)]),
     "fhs_linear_transform": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.c_int, _u64p, _vp,
@@ -989,6 +990,33 @@ def dot_product_many(ctx, query, chunks, rk=None, rescale=True):
     _check(_lib.fhs_dot_product_many(ctx._h, qq, J, dd, Cn, None if rk is None else rk._h, 1 if rescale else 0, hs),
            "dot_product_many")
     return [ciphertext(ctx, _vp(hs[c])) for c in range(Cn)]
+
+
+def multiply_relin_many(ctx, a, b, rk, rescale=True):
+    """Extension: [rescale](relinearize(multiply(a[i], b[i]))) for every pair at once (fhs_multiply_relin_many) --
+    the reference's ct_ct_multiply (fhe_rwkv_inference.py:103-108) per channel, limb-identical to the three calls per
+    pair, with one tensor launch, one batched key switch and one rescale launch per chunk of pairs.  b=None squares
+    (see square_many).  rk=None keeps the 3-component products; rescale=False keeps the product scale and the
+    level.  The inputs share one chain index, their scales may differ.  The results share one device block."""
+    a = list(a)
+    n = len(a)
+    aa = (_vp * max(n, 1))(*[c._h for c in a])
+    bb = None
+    if b is not None:
+        b = list(b)
+        if len(b) != n:
+            raise ValueError(f"multiply_relin_many: lists of different length ({n} and {len(b)})")
+        bb = (_vp * max(n, 1))(*[c._h for c in b])
+    outs = (_vp * max(n, 1))()
+    _check(_lib.fhs_multiply_relin_many(ctx._h, aa, bb, n, None if rk is None else rk._h, 1 if rescale else 0, outs),
+           "multiply_relin_many")
+    return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+
+
+def square_many(ctx, cts, rk, rescale=True):
+    """Extension: the reference's ct_ct_square (fhe_rwkv_inference.py:97-101) for every ciphertext of `cts` in one
+    call: multiply_relin_many with b = a, whose tensor kernel then reads each operand once."""
+    return multiply_relin_many(ctx, cts, None, rk, rescale)
 
 
 def dot_product_plain_many(ctx, query, pt_chunks, rescale=True):

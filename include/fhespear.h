@@ -315,6 +315,21 @@ fhs_status fhs_bsgs_giant_steps_device(fhs_context* ctx, const uint64_t* src, in
 fhs_status fhs_dot_product_many(fhs_context* ctx, const fhs_ciphertext* const* q, int J,
                                 const fhs_ciphertext* const* db, int C, const fhs_relin_key* rk,
                                 int rescale, fhs_ciphertext** outs);
+/* Extension (fri:97-108, ct_ct_square per FFN column and ct_ct_multiply per channel): n element-wise products.
+ *   out_array[i] = [rescale]( [relinearize]( a[i] (x) b[i] ) ),  i < n
+ * limb-identical to fhs_multiply, fhs_relinearize, fhs_rescale_to_next per pair, with ONE tensor launch, ONE batched
+ * key switch and ONE rescale launch per chunk of pairs (chunks bound the scratch, not n).  b = NULL squares: b = a.
+ * A non-null b[i] may be the same handle as a[i], and a handle may appear in several pairs.  rk = NULL: 3-component
+ * results.  rescale = 0: product scale and level kept.  n >= 1; every input has 2 components (else FHS_ERR_INVALID)
+ * and all inputs share one chain index (else FHS_ERR_LEVEL); scales may differ per pair: output i has scale
+ * a[i].scale * b[i].scale, divided by the dropped prime when rescaled; rescale at the last level is FHS_ERR_LEVEL.
+ * The relinearization follows the context's key-switch mode.  On failure nothing stays allocated and out_array is
+ * untouched.  Lifetime: the n results share one device block (as the plaintexts of a batch creator do), returned to
+ * the cache when the LAST of them is destroyed.  The inputs are not written and may be destroyed as soon as the
+ * call returns. */
+fhs_status fhs_multiply_relin_many(fhs_context* ctx, const fhs_ciphertext* const* a,
+                                   const fhs_ciphertext* const* b, int n, const fhs_relin_key* rk,
+                                   int rescale, fhs_ciphertext** out_array);
 /* Extension (no reference symbol): bg:198-203 + bg:361-432 on the device -- the D diagonals of the
  * D x D row-major matrix M1 (complex: M1 + i M2; M2 = NULL for real), group g = k / G rolled by g G,
  * tiled to N/2 slots, encoded at `scale` / `chain_index`.  Limb-identical to encode_*_vector_batch
