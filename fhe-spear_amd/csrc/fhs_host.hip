@@ -147,6 +147,9 @@ struct fhs_context {
     size_t cache_cap = 0;
     uint64_t cache_tick = 0;
     std::unordered_map<size_t, uint64_t> size_tick;   // last dalloc/dfree of each size
+    // fhs_debug_alloc_stats (testing hook): blocks evict_cold returned to the device, dalloc_fit calls that took a
+    // larger cached block, and the times seal_prepare emptied a non-empty correction cache because of its cap
+    uint64_t evicted_blocks = 0, fit_hits = 0, seal_corr_drops = 0;
     // kernel timer (bench): events around the timed kernel launches
     // per-kernel event timer (fhs_kernel_timer): bitmask of fhs::KernelId, completed pairs per id
     uint32_t timer_mask = 0;
@@ -331,6 +334,7 @@ static void evict_cold(fhs_context* c, size_t keep) {
     if (victims.empty()) return;
     ctx_sync(c);
     for (void* p : victims) (void)hipFree(p);
+    c->evicted_blocks += victims.size();
 }
 static hipError_t dalloc(fhs_context* c, uint64_t** p, size_t bytes) {
     if (c->debug_fail_alloc >= 0 && c->debug_fail_alloc-- == 0) return hipErrorOutOfMemory;
@@ -522,8 +526,11 @@ static hipError_t dalloc_fit(fhs_context* c, uint64_t** p, size_t* bytes) {
     for (auto& kv : c->free_blocks)
         if (!kv.second.empty() && kv.first >= *bytes && kv.first <= *bytes + *bytes / 2 && (!best || kv.first < best))
             best = kv.first;
+    const bool larger = best > *bytes;
     if (best) *bytes = best;
-    return dalloc(c, p, *bytes);
+    const hipError_t e = dalloc(c, p, *bytes);
+    if (e == hipSuccess && larger) ++c->fit_hits;
+    return e;
 }
 // `count` new plaintexts at chain index ci in one device block (PtSlab, dalloc_fit).  On failure nothing is
 // left allocated and outs[0..count) are null.
@@ -763,7 +770,10 @@ static hipError_t seal_prepare(fhs_context* c, std::vector<KsItem>& items, int l
     size_t need = 0;
     for (const KsItem& it : items)
         if (it.elt != 1 && !c->seal_corr.count({it.key, l})) need += seal_corr_bytes(c, l);
-    if (need && c->seal_corr_bytes + need > cap) drop_seal_corr(c, nullptr);
+    if (need && c->seal_corr_bytes + need > cap) {
+        if (!c->seal_corr.empty()) ++c->seal_corr_drops;
+        drop_seal_corr(c, nullptr);
+    }
     DevTmp mask(c);
     for (KsItem& it : items) {
         if (it.elt == 1) continue;
@@ -827,6 +837,7 @@ static fhs_status flush(fhs_context* c) {
         if (e == hipSuccess) sh = &c->seal_hoist;
         else if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) {
             for (auto& it : items) it.corr = nullptr;   // no room for the corrections: per-rotation path
+            ++c->seal_hoist.fallback;
             e = hipSuccess;
         }
         ht.mark("flush: seal corrections");
@@ -1490,6 +1501,14 @@ extern "C" fhs_status fhs_debug_fail_alloc(fhs_context* c, int nth, int* was_arm
     Guard g(c);
     if (was_armed) *was_armed = c->debug_fail_alloc >= 0;
     c->debug_fail_alloc = nth < 0 ? -1 : nth;
+    return FHS_OK;
+}
+extern "C" fhs_status fhs_debug_alloc_stats(fhs_context* c, uint64_t* out, int n) {
+    if (!c || !out || n < 0) return fail(FHS_ERR_INVALID, "debug_alloc_stats: bad args");
+    Guard g(c);
+    const uint64_t v[FHS_ALLOC_STATS_COUNT] = {c->cached_bytes,    c->cache_cap,     c->evicted_blocks, c->fit_hits,
+                                               c->seal_corr_bytes, c->seal_corr_cap, c->seal_corr_drops};
+    for (int i = 0; i < n && i < FHS_ALLOC_STATS_COUNT; ++i) out[i] = v[i];
     return FHS_OK;
 }
 extern "C" fhs_status fhs_debug_launch_ledger(int op, char* buf, uint64_t len, uint64_t* needed) {
@@ -2727,12 +2746,17 @@ extern "C" fhs_status fhs_apply_galois(fhs_context* c, const fhs_ciphertext* a, 
 extern "C" fhs_status fhs_rotate_many(fhs_context* c, const fhs_ciphertext* const* in, const int* steps, int n,
                                       const fhs_galois_keys* gk, fhs_ciphertext** out) {
     if (!c) return fail(FHS_ERR_INVALID, "null context");
+    if (!in || !steps || !out || n < 0) return fail(FHS_ERR_INVALID, "rotate_many: bad args");
     Guard g(c);
+    // a batch that fails part-way (an output's allocation, the flush) hands out nothing: the outputs made so far are
+    // destroyed -- the first of them still queued flushes the queue on its way out -- and their slots are null.  They
+    // used to stay allocated, and queued, behind an error their caller had no handle to answer with.
+    BatchOutT<fhs_ciphertext> bo(out, (size_t)n);
     for (int i = 0; i < n; ++i) {
         fhs_status s = queue_rotation(c, in[i], fhs_galois_elt_from_step(steps[i], c->N), gk, &out[i]);
         if (s != FHS_OK) return s;
     }
-    return flush(c);
+    return bo.keep(flush(c));
 }
 
 // ============================================================================ batched rotate-and-sum

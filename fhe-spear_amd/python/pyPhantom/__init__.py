@@ -197,6 +197,7 @@ _SIGS = {
     "fhs_debug_fail_alloc": (C.c_int, [_vp, C.c_int, _ip]),
     "fhs_debug_force_fork": (C.c_int, [_vp, C.c_int, _u64p]),
     "fhs_debug_launch_ledger": (C.c_int, [C.c_int, C.c_char_p, _u64, _u64p]),
+    "fhs_debug_alloc_stats": (C.c_int, [_vp, _u64p, C.c_int]),
 }
 # Fork-only symbols the reference probes with try/except AttributeError (bg:449-461, 382-391): if
 # the library lacks one (an older build, or FHESPEAR_DISABLE_SYMBOLS for tests), the Python names
@@ -395,10 +396,22 @@ class context:
 
     def seal_hoist_stats(self):
         """(hoisted, fallback): key-switch flushes in the SEAL convention that shared one decomposition per
-        input, and those that fell back to SEAL's per-rotation decomposition (a digit coefficient was 0)."""
+        input, and those that fell back to SEAL's per-rotation decomposition (a digit coefficient was 0, or no memory for the corrections)."""
         h, f = C.c_uint64(), C.c_uint64()
         _check(_lib.fhs_seal_hoist_stats(self._h, C.byref(h), C.byref(f)), "seal_hoist_stats")
         return int(h.value), int(f.value)
+
+    _ALLOC_STATS = ("cached_bytes", "cache_cap", "evicted", "fit", "seal_corr_bytes", "seal_corr_cap",
+                    "seal_corr_drops")
+
+    def debug_alloc_stats(self):
+        """Testing hook (fhs_debug_alloc_stats), read-only: the host allocator's state as a dict of integers --
+        cached_bytes and cache_cap of the block cache, blocks `evicted` to the device over that cap, batch
+        allocations that took a larger cached block (`fit`), seal_corr_bytes and seal_corr_cap of the SEAL
+        correction cache and the times the cap emptied it (seal_corr_drops).  Flushes and launches nothing."""
+        v = (C.c_uint64 * len(self._ALLOC_STATS))()
+        _check(_lib.fhs_debug_alloc_stats(self._h, v, len(v)), "debug_alloc_stats")
+        return dict(zip(self._ALLOC_STATS, (int(x) for x in v)))
 
     def galois_elts(self):
         """The Galois elements keys are made for (the params' set, or the SEAL/Phantom default

@@ -79,6 +79,31 @@ fhs_status fhs_debug_force_fork(fhs_context* ctx, int on, uint64_t* forked);
  * buf, len and needed are ignored by ARM and DISARM. */
 enum { FHS_LEDGER_ARM = 0, FHS_LEDGER_DISARM = 1, FHS_LEDGER_READ = 2 };
 fhs_status fhs_debug_launch_ledger(int op, char* buf, uint64_t len, uint64_t* needed);
+/* Testing hook (extension, replaces no pb symbol): the state of `ctx`'s host allocator, so that a test which bounds
+ * a cache can see the bound being applied.  Writes the first min(n, FHS_ALLOC_STATS_COUNT) of these to out:
+ *   FHS_ALLOC_CACHED_BYTES     bytes of freed device blocks kept in the block cache
+ *   FHS_ALLOC_CACHE_CAP        the bound on them (a quarter of the device's memory, or FHESPEAR_CACHE_BYTES as read
+ *                              when the context was created)
+ *   FHS_ALLOC_EVICTED          cached blocks returned to the device so far because the cache was over its bound
+ *                              (one per hipFree; the trims on out-of-memory and at destruction are not counted)
+ *   FHS_ALLOC_FIT              batch allocations so far that took a cached block larger than their request whole
+ *                              (up to 1.5x; an exact-size hit is not counted)
+ *   FHS_ALLOC_SEAL_CORR_BYTES  bytes of SEAL-convention hoisting corrections kept per (Galois key, level)
+ *   FHS_ALLOC_SEAL_CORR_CAP    the bound on them (1/16 of the device's memory, or FHESPEAR_SEAL_CORR_BYTES)
+ *   FHS_ALLOC_SEAL_CORR_DROPS  times a flush emptied a non-empty correction cache because its own corrections did
+ *                              not fit under the bound (a key's corrections leaving with the key are not counted)
+ * Read-only: it launches nothing, flushes no queued rotation and touches no device state. */
+enum {
+    FHS_ALLOC_CACHED_BYTES = 0,
+    FHS_ALLOC_CACHE_CAP = 1,
+    FHS_ALLOC_EVICTED = 2,
+    FHS_ALLOC_FIT = 3,
+    FHS_ALLOC_SEAL_CORR_BYTES = 4,
+    FHS_ALLOC_SEAL_CORR_CAP = 5,
+    FHS_ALLOC_SEAL_CORR_DROPS = 6,
+    FHS_ALLOC_STATS_COUNT = 7
+};
+fhs_status fhs_debug_alloc_stats(fhs_context* ctx, uint64_t* out, int n);
 
 /* ---- parameters (pb:78-98) ---- */
 /* pb:81 create_coeff_modulus: SEAL CoeffModulus::Create (largest primes = 1 mod 2N per size) */
@@ -135,7 +160,8 @@ fhs_status fhs_context_set_key_switch_mode(fhs_context* ctx, int mode);
 fhs_status fhs_context_key_switch_mode(const fhs_context* ctx, int* mode);
 /* SEAL convention: batched rotations of one ciphertext share one decomposition (the same limbs as SEAL's
  * per-rotation decomposition via a per-(Galois key, level) correction); a digit coefficient
- * equal to 0 falls back to the per-rotation path.  Counts of flushes taken each way. */
+ * equal to 0 falls back to the per-rotation path, and so does a flush whose corrections could not be allocated
+ * (out of memory).  Counts of flushes taken each way. */
 fhs_status fhs_seal_hoist_stats(fhs_context* ctx, uint64_t* hoisted, uint64_t* fallback);
 fhs_status fhs_public_key_export(fhs_context* ctx, const fhs_public_key* pk, uint64_t* host /* [2][L0][N] */);
 fhs_status fhs_galois_keys_bytes(const fhs_galois_keys* gk, uint64_t* bytes);
@@ -236,7 +262,8 @@ fhs_status fhs_rotate(fhs_context* ctx, const fhs_ciphertext* a, int step, const
 /* pb:201 apply_galois with an explicit element */
 fhs_status fhs_apply_galois(fhs_context* ctx, const fhs_ciphertext* a, uint64_t elt, const fhs_galois_keys* gk,
                             fhs_ciphertext** out);
-/* batch of rotations of possibly different inputs: out[i] = rotate(in[i], steps[i]) */
+/* batch of rotations of possibly different inputs: out[i] = rotate(in[i], steps[i]).  On failure nothing is handed
+ * out: out[0..n) are null and the outputs already made are destroyed. */
 fhs_status fhs_rotate_many(fhs_context* ctx, const fhs_ciphertext* const* in, const int* steps, int n,
                            const fhs_galois_keys* gk, fhs_ciphertext** out);
 /* Extension (fri:71-75): out[i] = x_K, where x_0 = in[i] and x_{k+1} = x_k + rotate(x_k, stride * 2^k),
