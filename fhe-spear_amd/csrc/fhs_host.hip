@@ -2541,7 +2541,6 @@ static fhs_status same_level(const fhs_ciphertext* a, const fhs_ciphertext* b) {
     if (a->ci != b->ci) return fail(FHS_ERR_LEVEL, "operands are at different chain indices");
     return FHS_OK;
 }
-static bool scales_close(double a, double b) { return std::fabs(a - b) <= 1e-9 * std::max(std::fabs(a), std::fabs(b)); }
 
 static fhs_status binop(fhs_context* c, int op, const fhs_ciphertext* a, const fhs_ciphertext* b, fhs_ciphertext** out) {
     if (!a || !b || !out) return fail(FHS_ERR_INVALID, "null argument");
@@ -3167,6 +3166,109 @@ extern "C" fhs_status fhs_multiply_relin_many(fhs_context* c, const fhs_cipherte
     }
     std::copy(cts.begin(), cts.end(), out_array);
     return bo.keep(FHS_OK);
+}
+
+// ============================================================================ plaintext-weighted sums of ciphertexts
+// out[i] = sum_j rescale_to_next(multiply_plain(in[j], P_ij)), P_ij the constant plaintext round(W[j ldw + i] scale)
+// (fri:79-94, ct_pt_weighted_sum for every output column at once), limb-identical to that loop although the rescale
+// rounds per term: with L = l - 1, inv_m = q_L^-1 mod q_m and d_j = INTT_L(in[j] limb L),
+//   out_i[comp][m] = sum_j (k_ijm inv_m) c_j[comp][m] - inv_m NTT_m(S_i[comp] mod q_m),
+//   S_i[comp][n]   = sum_j centre(k_ijL d_j[comp][n] mod q_L)          (DESIGN.md section 3 "weighted sums").
+// One launch takes every input's last limb to coefficient form (k_rescale_intt over a pointer list); then per chunk of
+// outputs (fhs_tables.h weighted_sums_chunks) four launches whatever F and E: the rounding sums (k_scalar,
+// SCALAR_WSUM_ROUND), their residues and NTT (launch_encode_int128: two) and the weighted sums (k_scalar,
+// SCALAR_WSUM_ACC) straight into the chunk's slice of the results' block.
+extern "C" fhs_status fhs_weighted_sums(fhs_context* c, const fhs_ciphertext* const* in, int F, const double* W,
+                                        int64_t ldw, int E, double scale, fhs_ciphertext** out_array) {
+    ENTER(c);
+    const bool null_arg = !in || !W || !out_array;
+    const int cnt = (null_arg || F < 1 || F > kWsumMaxF) ? 0 : F;
+    std::vector<int> ncomp(cnt), cis(cnt);
+    std::vector<double> scs(cnt);
+    std::vector<const uint64_t*> ptrs(cnt);
+    for (int j = 0; j < cnt; ++j) {
+        if (!in[j]) return fail(FHS_ERR_INVALID, "null argument");
+        LIVE(in[j]);
+        ncomp[j] = in[j]->ncomp;
+        cis[j] = in[j]->ci;
+        scs[j] = in[j]->scale;
+        ptrs[j] = in[j]->d;
+    }
+    WsumErr cls = WSUM_INVALID;
+    if (const char* bad = weighted_sums_error(null_arg, F, E, ldw, scale, ncomp.data(), cis.data(), scs.data(), c->L0, &cls))
+        return fail(cls == WSUM_LEVEL ? FHS_ERR_LEVEL : cls == WSUM_SCALE ? FHS_ERR_SCALE : FHS_ERR_INVALID, bad);
+    const int ci = in[0]->ci, l = in[0]->l, lm = l - 1;
+    if (c->N % 2) return fail(FHS_ERR_INVALID, "weighted_sums: poly_modulus_degree must be even");
+    WsumTables Wt;
+    if (const char* bad = weighted_sums_tables(W, ldw, F, E, scale, c->q.data(), l, fhs::wsum_tile(), Wt))
+        return fail(FHS_ERR_INVALID, bad);
+    const size_t N = c->N;
+    const std::vector<std::pair<int, int>> chunks = weighted_sums_chunks(E, F, N, l);
+    const size_t Rmax = (size_t)chunks[0].second;
+    // every allocation before the first launch; out_array is written only on success
+    uint64_t *dco = nullptr, *planes = nullptr, *tcorr = nullptr, *wdev = nullptr, *tptrs = nullptr;
+    HIPCHK(scratch(c, fhs_context::SCR_RESCALE, 16 * (size_t)F * N, &dco), "weighted_sums");
+    HIPCHK(scratch(c, fhs_context::SCR_BSGS_SUM, 32 * Rmax * N, &planes), "weighted_sums");
+    HIPCHK(scratch(c, fhs_context::SCR_BSGS_INNER, 16 * Rmax * lm * N, &tcorr), "weighted_sums");
+    HIPCHK(scratch(c, fhs_context::SCR_BSGS_WS, 8 * (Wt.wl.size() + Wt.wt.size()), &wdev), "weighted_sums");
+    HIPCHK(scratch(c, fhs_context::SCR_ENC_PTRS, 16 * Rmax, &tptrs), "weighted_sums");
+    std::vector<fhs_ciphertext*> held((size_t)E), cts;
+    BatchOutT<fhs_ciphertext> bo(held.data(), (size_t)E);
+    fhs_status s = new_cts(c, E, 2, ci + 1, in[0]->scale * scale / (double)c->q[l - 1], cts);
+    if (s != FHS_OK) return s;
+    std::copy(cts.begin(), cts.end(), held.begin());
+    uint64_t* const res = cts[0]->d;   // [E][2][l - 1][N]: one block (new_cts), or the single ciphertext
+    uint64_t* const wt_dev = wdev + Wt.wl.size();
+    std::vector<uint64_t*> tp(2 * Rmax);
+    for (size_t v = 0; v < 2 * Rmax; ++v) tp[v] = tcorr + v * lm * N;
+    HIPCHK(stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * ptrs.size()), "weighted_sums");
+    HIPCHK(stage_h2d(c, tptrs, tp.data(), sizeof(void*) * tp.size()), "weighted_sums");
+    HIPCHK(stage_h2d(c, wdev, Wt.wl.data(), 8 * Wt.wl.size()), "weighted_sums");
+    HIPCHK(stage_h2d(c, wt_dev, Wt.wt.data(), 8 * Wt.wt.size()), "weighted_sums");
+    const uint64_t* const* din = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
+    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    HIPCHK(fhs::launch_last_limbs_intt(c->T, din, F, l, dco, c->st, tm), "weighted_sums");
+    for (const auto& ch : chunks)
+        HIPCHK(fhs::launch_wsum_chunk(c->T, din, dco, wdev, wt_dev, F, Wt.Epad, ch.first, ch.second, l, planes, tcorr,
+                                      reinterpret_cast<fhs::u64* const*>(tptrs), res, c->st, tm), "weighted_sums");
+    std::copy(cts.begin(), cts.end(), out_array);
+    return bo.keep(FHS_OK);
+}
+
+// Test hooks: the per-coefficient routines of fhs_weighted_sums' two pointwise stages (fhs_modarith.h wsum_round_*,
+// wsum_*) on the host, in the kernel's order.  round: S = sum_j centre(k_j d_j mod qL) as the signed 128-bit
+// hi 2^64 + lo; accumulate: (sum_j kprime_j c_j + wT t) mod q.  Operands must be < q < 2^60.
+extern "C" fhs_status fhs_debug_wsum_round(uint64_t qL, const uint64_t* k, const uint64_t* d, int F, int64_t* hi,
+                                           uint64_t* lo) {
+    if (!k || !d || !hi || !lo || F < 1 || F > kWsumMaxF) return fail(FHS_ERR_INVALID, "debug_wsum_round: bad argument");
+    if (qL < 3 || !(qL & 1) || qL >= (1ull << 60)) return fail(FHS_ERR_INVALID, "debug_wsum_round: q must be odd and < 2^60");
+    WsumRound s{0, 0, 0};
+    for (int j = 0; j < F; ++j) {
+        if (k[j] >= qL || d[j] >= qL) return fail(FHS_ERR_INVALID, "debug_wsum_round: operands must be < q");
+        wsum_round_term(s, d[j], k[j], h_shoup(k[j], qL), qL);
+    }
+    wsum_round_finish(s, qL, *hi, *lo);
+    return FHS_OK;
+}
+extern "C" fhs_status fhs_debug_wsum_accumulate(uint64_t q, const uint64_t* kprime, const uint64_t* cj, int F, uint64_t wT,
+                                                uint64_t t, uint64_t* out) {
+    if (!kprime || !cj || !out || F < 1 || F > kWsumMaxF) return fail(FHS_ERR_INVALID, "debug_wsum_accumulate: bad argument");
+    if (q < 3 || !(q & 1) || q >= (1ull << 60)) return fail(FHS_ERR_INVALID, "debug_wsum_accumulate: q must be odd and < 2^60");
+    if (wT >= q || t >= q) return fail(FHS_ERR_INVALID, "debug_wsum_accumulate: operands must be < q");
+    const uint64_t w = pm_word(q, 14);
+    const hu128 r = ~(hu128)0 / q;
+    const RedU R{q, (uint64_t)r, (uint64_t)(r >> 64), (unsigned)(w & 127), (unsigned)((w >> 8) & 0xFFFFFFFFu), false, false};
+    const unsigned fmask = wsum_fmask(q);
+    Wsum s;
+    wsum_clear(s);
+    for (int j = 0; j < F; ++j) {
+        if (kprime[j] >= q || cj[j] >= q) return fail(FHS_ERR_INVALID, "debug_wsum_accumulate: operands must be < q");
+        wsum_mac(s, unpack30(pack30(kprime[j])), split30(cj[j]));
+        wsum_after(s, j + 1, fmask, R);
+    }
+    wsum_mac(s, unpack30(pack30(wT)), split30(t));
+    *out = wsum_finish(s, R);
+    return FHS_OK;
 }
 
 // Test hook: k_dot_tensor's per-coefficient schedule (dot3_term / dot3_finish, fhs_modarith.h: accumulate, fold,

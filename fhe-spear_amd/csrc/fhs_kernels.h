@@ -110,7 +110,8 @@ hipError_t launch_seal_corr(const DevTables& T, const u64* key, const u64* akey,
 // Optional per-kernel event timer (bench.py): rec(ctx, id, begin, stream) is called around launches.
 enum KernelId { KID_BSGS_INNER = 0, KID_MODUP = 1, KID_KS_IP = 2, KID_MODDOWN = 3, KID_KS_INTT = 4, KID_SPECIAL_INTT = 5,
                 KID_GIANT_SUM = 6, KID_GIANT_FINAL = 7, KID_RESCALE = 8, KID_DOT_TENSOR = 9, KID_ENCRYPT_PK = 10,
-                KID_COUNT = 11 };
+                // fhs_weighted_sums' four stages: last-limb INTTs, rounding sums, their residues + NTT, weighted sums
+                KID_WSUM_INTT = 11, KID_WSUM_ROUND = 12, KID_WSUM_ENCODE = 13, KID_WSUM_ACC = 14, KID_COUNT = 15 };
 struct KTimer {
     void* ctx;
     void (*rec)(void* ctx, int id, int begin, hipStream_t st);
@@ -285,9 +286,24 @@ struct ScalarConsts {
     u64 v[kMaxScalarLimbs];
     u64 vs[kMaxScalarLimbs];
 };
-enum ScalarOp { SCALAR_MUL = 0, SCALAR_ADD = 1 };
+enum ScalarOp { SCALAR_MUL = 0, SCALAR_ADD = 1, SCALAR_WSUM_ROUND = 2, SCALAR_WSUM_ACC = 3 };
 hipError_t launch_scalar(const DevTables& T, int op, const u64* a, u64* out, int ncomp, int l, const ScalarConsts& K,
                          hipStream_t st);
+// fhs_weighted_sums (k_scalar's SCALAR_WSUM_* ops): F inputs, the weight tables' row length Epad, the chunk's first
+// output i0 and its R outputs
+struct WsumArgs {
+    int F, Epad, i0, R;
+};
+int wsum_tile();   // outputs per thread tile: the weight tables are padded for it (fhs_tables.h weighted_sums_tables)
+// stage 1, once per call: the last limbs of the F inputs' components in coefficient form, dco [F][2][N]
+hipError_t launch_last_limbs_intt(const DevTables& T, const u64* const* ins_dev, int count, int l, u64* dco, hipStream_t st,
+                                  const KTimer* tm = nullptr);
+// stages 2-4 for outputs [i0, i0 + R): the rounding sums into `planes` (hi then lo, [2 R][N] each), their residues
+// and NTT at l - 1 limbs into tcorr [2 R][l - 1][N] (tptrs_dev: its 2 R polynomial addresses), the weighted sums into
+// res [E][2][l - 1][N] at output i0.  wl_dev [2][F][Epad], wt_dev [l - 1][F + 1][Epad].  Four launches.
+hipError_t launch_wsum_chunk(const DevTables& T, const u64* const* ins_dev, const u64* dco, const u64* wl_dev,
+                             const u64* wt_dev, int F, int Epad, int i0, int R, int l, u64* planes, u64* tcorr,
+                             u64* const* tptrs_dev, u64* res, hipStream_t st, const KTimer* tm = nullptr);
 // ModRaise (bootstrapping): limb 0 of each component -> centred lift to all L0 data limbs (NTT form)
 hipError_t launch_mod_raise(const DevTables& T, const u64* in, int l, u64* out, u64* scratch, int ncomp,
                             hipStream_t st);

@@ -609,12 +609,13 @@ hipError_t launch_galois_perm(const DevTables& T, const u64* in, u64* out, int l
 // ============================================================================ rescale (pb:185)
 // 1) last limb of each component -> coefficient form (scratch[comp])
 template <int LOGN, bool H = ntt_half<LOGN>()>
-__global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_rescale_intt(DevTables T, const u64* in, u64* scratch, int l) {
+__global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_rescale_intt(DevTables T, const u64* in, const u64* const* ins, u64* scratch, int l) {
     constexpr int N = 1 << LOGN;
     __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, H>()];
     const int comp = blockIdx.x, pi = l - 1;
     const PrimeK& P = PK(T, pi);
-    const u64* src = in + ((size_t)comp * l + pi) * N;
+    // the components of one polynomial array, or (ins: fhs_weighted_sums) the two of each listed ciphertext
+    const u64* src = ins ? ins[comp >> 1] + ((size_t)(comp & 1) * l + pi) * N : in + ((size_t)comp * l + pi) * N;
     u64* dst = scratch + (size_t)comp * N;
     const u64 half = P.q >> 1, q = P.q;
     inv_limb<LOGN, FHS_NTT_RL, H>(lds, threadIdx.x, T.tw_inv + (size_t)pi * N * 2, q, P.ninv, P.ninv_s, P.w1ninv,
@@ -738,10 +739,23 @@ hipError_t launch_rescale(const DevTables& T, const u64* in, u64* out, u64* scra
                 break;
             }
         }
-        FHS_NTT_LAUNCH(k_rescale_intt, ncomp, dim3(ncomp), st, T, in, scratch, l);
+        FHS_NTT_LAUNCH(k_rescale_intt, ncomp, dim3(ncomp), st, T, in, static_cast<const u64* const*>(nullptr), scratch, l);
         FHS_NTT_LAUNCH(k_rescale_ntt, (l - 1) * ncomp, dim3(l - 1, ncomp), st, T, in, scratch, out, l);
     });
     FHS_TMARK(tm, KID_RESCALE, 0, st);
+    return hipGetLastError();
+}
+
+// fhs_weighted_sums stage 1: the last limb of both components of `count` ciphertexts (device pointer list) to
+// coefficient form in ONE launch, dco[j][comp][N] = INTT(limb l - 1) + floor(q_{l-1} / 2) as k_rescale_intt leaves it
+hipError_t launch_last_limbs_intt(const DevTables& T, const u64* const* ins_dev, int count, int l, u64* dco, hipStream_t st,
+                                  const KTimer* tm) {
+    if (count < 1 || count > 65535 || l < 1) return hipErrorInvalidValue;
+    FHS_TMARK(tm, KID_WSUM_INTT, 1, st);
+    FHS_DISPATCH_LOGN(T.logN, {
+        FHS_NTT_LAUNCH(k_rescale_intt, 2 * count, dim3(2 * count), st, T, static_cast<const u64*>(nullptr), ins_dev, dco, l);
+    });
+    FHS_TMARK(tm, KID_WSUM_INTT, 0, st);
     return hipGetLastError();
 }
 
@@ -3487,26 +3501,182 @@ hipError_t launch_crt_compose(const CrtConsts& K, const u64* limbs, double* out,
 // Constant products / sums (ckks_bootstrapper: pre-scale, EvalMod's Chebyshev coefficients and
 // constants, scale alignment).  A constant polynomial c has NTT image c in every slot, so both ops
 // are slot-wise: MULC multiplies every component by c_i (Shoup), ADDC adds c_i to component 0.
-__global__ void k_scalar(DevTables T, int op, const u64* __restrict__ a, u64* __restrict__ out, int ncomp, int l,
-                         ScalarConsts K) {
+// The same kernel carries the two pointwise stages of fhs_weighted_sums (plaintext-weighted sums of ciphertexts:
+// every plaintext is a constant, so both stages are slot- / coefficient-wise with workgroup-uniform weights):
+//   SCALAR_WSUM_ROUND  S_i[comp][n] = sum_j centre(kL_ij d_j[comp][n] mod qL) as the hi / lo planes launch_encode_int128
+//                      reads (coefficient domain, d_j from launch_last_limbs_intt);
+//   SCALAR_WSUM_ACC    out_i[comp][m] = sum_j k'_ijm c_j[comp][m] + (q_m - inv_m) T_i[comp][m] over the data limbs.
+// Both: a thread owns two adjacent coefficients (16-byte accesses) of a tile of kWsumTile outputs, so every input
+// word is loaded once per tile; the tile's weights are consecutive words read by scalar loads.  The per-coefficient
+// schedule and its bounds are wsum_round_* / wsum_* (fhs_modarith.h).  grid: (N / 512, components [x data limbs], tiles).
+// kWsumTile = 4: with 8 the accumulators alone (2 x 8 x 10 registers) pass 128 VGPRs and the kernel, whose registers
+// the constant ops share, drops to one wave per SIMD less (DESIGN.md section 3 "weighted sums").
+#ifndef FHS_WSUM_TILE
+#define FHS_WSUM_TILE 4
+#endif
+constexpr int kWsumTile = FHS_WSUM_TILE;
+constexpr int kWsumBatch = 4;   // input loads in flight per thread (SCALAR_WSUM_ACC)
+// an input taken from the pointer list: device memory, said so for a global (not flat) 16-byte load, as tensor_ld
+__device__ __forceinline__ ulonglong2 wsum_ld(const u64* p) {
+    const tensor_v2 v = tensor_ld(p);
+    return make_ulonglong2(v.x, v.y);
+}
+__device__ __forceinline__ void wsum_round_tile(const DevTables& T, const u64* __restrict__ dco, const u64* __restrict__ wl,
+                                                u64* __restrict__ planes, int l, const WsumArgs& A) {
+    constexpr int TO = kWsumTile;
+    const int N = T.N, e = (blockIdx.x * 256 + threadIdx.x) * 2;
+    if (e >= N) return;
+    const int comp = blockIdx.y, tl = blockIdx.z * TO;   // the tile's first output inside the chunk
+    const u64 qL = rfl64(PK(T, l - 1).q), half = qL >> 1;
+    const u64* __restrict__ w = wl + A.i0 + tl;          // kL of (output, input j) at [j][Epad], its Shoup word at [F + j][Epad]
+    WsumRound s[TO][2];
+#pragma unroll
+    for (int t = 0; t < TO; ++t) s[t][0] = s[t][1] = WsumRound{0, 0, 0};
+    for (int j = 0; j < A.F; ++j) {
+        const ulonglong2 x = *reinterpret_cast<const ulonglong2*>(dco + ((size_t)j * 2 + comp) * N + e);
+        const u64 d0 = submod(x.x, half, qL), d1 = submod(x.y, half, qL);   // stage 1 left d + half
+#pragma unroll
+        for (int t = 0; t < TO; ++t) {
+            const u64 k = w[(size_t)j * A.Epad + t], ks = w[((size_t)A.F + j) * A.Epad + t];
+            wsum_round_term(s[t][0], d0, k, ks, qL);
+            wsum_round_term(s[t][1], d1, k, ks, qL);
+        }
+    }
+    u64* __restrict__ lo_plane = planes + (size_t)2 * A.R * N;
+#pragma unroll
+    for (int t = 0; t < TO; ++t) {
+        if (tl + t >= A.R) break;
+        int64_t h0, h1;
+        u64 l0, l1;
+        wsum_round_finish(s[t][0], qL, h0, l0);
+        wsum_round_finish(s[t][1], qL, h1, l1);
+        const size_t at = ((size_t)(tl + t) * 2 + comp) * N + e;
+        *reinterpret_cast<ulonglong2*>(planes + at) = make_ulonglong2((u64)h0, (u64)h1);
+        *reinterpret_cast<ulonglong2*>(lo_plane + at) = make_ulonglong2(l0, l1);
+    }
+}
+__device__ __forceinline__ void wsum_acc_tile(const DevTables& T, const u64* const* __restrict__ ins,
+                                              const u64* __restrict__ wt, const u64* __restrict__ tcorr, u64* __restrict__ out,
+                                              int l, const WsumArgs& A) {
+    constexpr int TO = kWsumTile, B = kWsumBatch;
+    const int N = T.N, e = (blockIdx.x * 256 + threadIdx.x) * 2;
+    if (e >= N) return;
+    const int lm = l - 1, m = blockIdx.y % lm, comp = blockIdx.y / lm, tl = blockIdx.z * TO, F = A.F;
+    const RedU R = redu(PK(T, m));
+    const unsigned fmask = wsum_fmask(R.q);
+    // split-30 packed weights of limb m: row j < F the inputs', row F the correction's q_m - inv_m
+    const u64* __restrict__ w = wt + (size_t)m * (F + 1) * A.Epad + A.i0 + tl;
+    const size_t off = ((size_t)comp * l + m) * N + e;
+    Wsum s[TO][2];
+#pragma unroll
+    for (int t = 0; t < TO; ++t) {
+        wsum_clear(s[t][0]);
+        wsum_clear(s[t][1]);
+    }
+    auto mac_tile = [&](int row, int t, const ulonglong2& x) {
+        const Split30 k = unpack30(w[(size_t)row * A.Epad + t]);
+        wsum_mac(s[t][0], k, split30(x.x));
+        wsum_mac(s[t][1], k, split30(x.y));
+    };
+    auto after = [&](int done) {
+#pragma unroll
+        for (int t = 0; t < TO; ++t) {
+            wsum_after(s[t][0], done, fmask, R);
+            wsum_after(s[t][1], done, fmask, R);
+        }
+    };
+    ulonglong2 x[B];
+    const int nb = F / B;
+    if (nb > 0) {
+#pragma unroll
+        for (int u = 0; u < B; ++u) x[u] = wsum_ld(ins[u] + off);
+    }
+    int j = 0;
+    for (int bi = 0; bi < nb; ++bi, j += B) {
+        const u64* const* nxt = bi + 1 < nb ? ins + j + B : nullptr;
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+#pragma unroll
+            for (int t = 0; t < TO; ++t) mac_tile(j + u, t, x[u]);
+            if (nxt) x[u] = wsum_ld(nxt[u] + off);   // slot u's refill: the next batch
+        }
+        after(j + B);   // FOLD and the window are multiples of the batch
+    }
+    for (; j < F; ++j) {   // < kWsumBatch left
+        const ulonglong2 y = wsum_ld(ins[j] + off);
+#pragma unroll
+        for (int t = 0; t < TO; ++t) mac_tile(j, t, y);
+        after(j + 1);
+    }
+#pragma unroll
+    for (int t = 0; t < TO; ++t) {
+        if (tl + t >= A.R) break;
+        const ulonglong2 tv =
+            *reinterpret_cast<const ulonglong2*>(tcorr + (((size_t)(tl + t) * 2 + comp) * lm + m) * N + e);
+        mac_tile(F, t, tv);
+        u64* o = out + (((size_t)(A.i0 + tl + t) * 2 + comp) * lm + m) * N + e;
+        *reinterpret_cast<ulonglong2*>(o) = make_ulonglong2(wsum_finish(s[t][0], R), wsum_finish(s[t][1], R));
+    }
+}
+static_assert(8 % kWsumBatch == 0 && kWsumWindow % kWsumBatch == 0, "folds and windows fall on batch ends");
+__global__ void __launch_bounds__(256) k_scalar(DevTables T, int op, const u64* __restrict__ a, u64* __restrict__ out,
+                                                int ncomp, int l, ScalarConsts K, const u64* const* __restrict__ ins,
+                                                const u64* __restrict__ wtab, const u64* __restrict__ aux, WsumArgs A) {
+    if (op == SCALAR_WSUM_ROUND) return wsum_round_tile(T, a, wtab, out, l, A);
+    if (op == SCALAR_WSUM_ACC) return wsum_acc_tile(T, ins, wtab, aux, out, l, A);
+    // the constant ops: two 16-byte pairs per thread and pass, both loads issued before the first product -- the
+    // weighted-sum tiles set this kernel's registers (3 waves per SIMD), so the bytes in flight come from the thread
     const int N = T.N;
-    const size_t total = (size_t)ncomp * l * N;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total;
-         idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t li = idx / N;
-        const int i = (int)(li % l), comp = (int)(li / l);
-        const u64 q = PK(T, i).q, x = a[idx];
-        u64 r;
-        if (op == SCALAR_MUL) r = shoup(x, K.v[i], K.vs[i], q);
-        else r = comp == 0 ? addmod(x, K.v[i], q) : x;
-        out[idx] = r;
+    const size_t pairs = (size_t)ncomp * l * N / 2, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t p0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p0 < pairs; p0 += 2 * stride) {
+        const size_t p1 = p0 + stride;
+        const ulonglong2 x0 = *reinterpret_cast<const ulonglong2*>(a + 2 * p0);
+        const ulonglong2 x1 = p1 < pairs ? *reinterpret_cast<const ulonglong2*>(a + 2 * p1) : make_ulonglong2(0, 0);
+        auto one = [&](size_t p, const ulonglong2& x) {
+            const size_t li = 2 * p / N;   // N is even: a pair lies in one limb
+            const int i = (int)(li % l), comp = (int)(li / l);
+            const u64 q = PK(T, i).q;
+            ulonglong2 r = x;
+            if (op == SCALAR_MUL) r = make_ulonglong2(shoup(x.x, K.v[i], K.vs[i], q), shoup(x.y, K.v[i], K.vs[i], q));
+            else if (comp == 0) r = make_ulonglong2(addmod(x.x, K.v[i], q), addmod(x.y, K.v[i], q));
+            *reinterpret_cast<ulonglong2*>(out + 2 * p) = r;
+        };
+        one(p0, x0);
+        if (p1 < pairs) one(p1, x1);
     }
 }
 hipError_t launch_scalar(const DevTables& T, int op, const u64* a, u64* out, int ncomp, int l, const ScalarConsts& K,
                          hipStream_t st) {
-    if (l > kMaxScalarLimbs) return hipErrorInvalidValue;
-    FHS_LAUNCH(k_scalar, dim3(eltwise_grid((size_t)ncomp * l * T.N)), dim3(256), 0, st, T, op, a, out, ncomp, l,
-               K);
+    if (l > kMaxScalarLimbs || (op != SCALAR_MUL && op != SCALAR_ADD) || T.N % 2) return hipErrorInvalidValue;
+    FHS_LAUNCH(k_scalar, dim3(eltwise_grid(((size_t)ncomp * l * T.N + 3) / 4)), dim3(256), 0, st, T, op, a, out, ncomp, l,
+               K, static_cast<const u64* const*>(nullptr), static_cast<const u64*>(nullptr),
+               static_cast<const u64*>(nullptr), WsumArgs{0, 0, 0, 0});
+    return hipGetLastError();
+}
+int wsum_tile() { return kWsumTile; }
+hipError_t launch_wsum_chunk(const DevTables& T, const u64* const* ins_dev, const u64* dco, const u64* wl_dev,
+                             const u64* wt_dev, int F, int Epad, int i0, int R, int l, u64* planes, u64* tcorr,
+                             u64* const* tptrs_dev, u64* res, hipStream_t st, const KTimer* tm) {
+    const int tiles = (R + kWsumTile - 1) / kWsumTile;
+    if (F < 1 || R < 1 || l < 2 || tiles > 65535 || 2 * (l - 1) > 65535 || 2 * R > 65535 || T.N % 2) return hipErrorInvalidValue;
+    const WsumArgs A{F, Epad, i0, R};
+    static const ScalarConsts none = {};
+    const unsigned gx = (unsigned)((T.N + 511) / 512);
+    FHS_TMARK(tm, KID_WSUM_ROUND, 1, st);
+    FHS_LAUNCH(k_scalar, dim3(gx, 2, tiles), dim3(256), 0, st, T, (int)SCALAR_WSUM_ROUND, dco, planes, 2, l, none,
+               static_cast<const u64* const*>(nullptr), wl_dev, static_cast<const u64*>(nullptr), A);
+    FHS_TMARK(tm, KID_WSUM_ROUND, 0, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    FHS_TMARK(tm, KID_WSUM_ENCODE, 1, st);
+    e = launch_encode_int128(T, reinterpret_cast<const int64_t*>(planes), planes + (size_t)2 * R * T.N, 2 * R, tptrs_dev,
+                             l - 1, st);
+    FHS_TMARK(tm, KID_WSUM_ENCODE, 0, st);
+    if (e != hipSuccess) return e;
+    FHS_TMARK(tm, KID_WSUM_ACC, 1, st);
+    FHS_LAUNCH(k_scalar, dim3(gx, 2 * (l - 1), tiles), dim3(256), 0, st, T, (int)SCALAR_WSUM_ACC,
+               static_cast<const u64*>(nullptr), res, 2, l, none, ins_dev, wt_dev, static_cast<const u64*>(tcorr), A);
+    FHS_TMARK(tm, KID_WSUM_ACC, 0, st);
     return hipGetLastError();
 }
 

@@ -438,6 +438,58 @@ __host__ __device__ __forceinline__ void dot3_finish(Dot3& s, const RedU& R, con
         out[2] = addmod(out[2], prev[2], R.q);
     }
 }
+// ---- plaintext-weighted sums of ciphertexts at one coefficient (k_scalar's SCALAR_WSUM_ROUND / SCALAR_WSUM_ACC in
+// fhs_kernels.hip; the host test hooks fhs_debug_wsum_round / fhs_debug_wsum_accumulate run the same routines).
+// Shoup product with a plain 64-bit high multiply (host and device): w a mod q in [0, q) for any 64-bit a, w < q.
+__host__ __device__ __forceinline__ u64 shoup_hd(u64 a, u64 w, u64 wp, u64 q) {
+    return csub(a * w - umulhi64_hd(a, wp) * q, q);
+}
+// Rounding sum: S = sum_j centre(k_j d_j mod qL), centre(u) = u for u <= qL >> 1, else u - qL (qL is odd).  Kept as the
+// unsigned sum of the residues u (< 2^60 each, F <= 4096 terms: < 2^72) and the count of those above the half;
+// S = sum - neg qL as a signed 128-bit integer, |S| <= F qL / 2.
+struct WsumRound {
+    u64 lo, hi, neg;
+};
+__host__ __device__ __forceinline__ void wsum_round_term(WsumRound& s, u64 d, u64 k, u64 ks, u64 qL) {
+    const u64 u = shoup_hd(d, k, ks, qL);
+    s.lo += u;
+    s.hi += (u64)(s.lo < u);
+    s.neg += (u64)(u > (qL >> 1));
+}
+__host__ __device__ __forceinline__ void wsum_round_finish(const WsumRound& s, u64 qL, int64_t& hi, u64& lo) {
+    const u64 pl = s.neg * qL, ph = umulhi64_hd(s.neg, qL);
+    lo = s.lo - pl;
+    hi = (int64_t)(s.hi - ph - (u64)(s.lo < pl));
+}
+// Weighted sum: sum_p k_p x_p mod q over F + 1 products (the F inputs, then the rounding correction), residues and
+// weights < q < 2^60.  Split-30 partials in an Acc3, folded into the 128-bit sum every FOLD = fmask + 1 products
+// (8 for any prime, 16 for q < 2^59: the bounds of dot3_term), and ONE reduction per window of kWsumWindow = 64
+// products, whose residue restarts the 128-bit sum: never more than q + 64 2^120 < 2^127.  wsum_after(done) is
+// called with the number of products taken so far wherever that may be a multiple of FOLD; the correction comes
+// last, after at most fmask pending products and 63 since the last reduction.
+constexpr int kWsumWindow = kDotWindowMax;
+struct Wsum {
+    Acc3 a;
+    u128 c;
+};
+__host__ __device__ __forceinline__ void wsum_clear(Wsum& s) {
+    s.a = Acc3{0, 0, 0};
+    s.c = u128{0, 0};
+}
+__host__ __device__ __forceinline__ unsigned wsum_fmask(u64 q) { return q < (1ull << 59) ? 15u : 7u; }
+__host__ __device__ __forceinline__ void wsum_mac(Wsum& s, Split30 k, Split30 x) { acc3_mac(s.a, k, x); }
+__host__ __device__ __forceinline__ void wsum_after(Wsum& s, int done, unsigned fmask, const RedU& R) {
+    if ((done & fmask) == 0) acc3_fold(s.c, s.a);
+    if ((done & (kWsumWindow - 1)) == 0) {
+        s.c.lo = reduce128(s.c.lo, s.c.hi, R);
+        s.c.hi = 0;
+    }
+}
+__host__ __device__ __forceinline__ u64 wsum_finish(Wsum& s, const RedU& R) {
+    acc3_fold(s.c, s.a);
+    return reduce128(s.c.lo, s.c.hi, R);
+}
+
 // Any 64-bit value of a pseudo-Mersenne prime (b >= 41) to [0, q): one fold, one subtraction.
 __device__ __forceinline__ u64 pm_fold64(u64 x, const RedU& R) {
     const u64 h = x >> R.b;

@@ -1,7 +1,8 @@
 // fhs_tables.h -- host-only derivation of a context's parameter tables: the host number theory, the
 // coefficient-modulus search, argument validation for fhs_context_create and fhs_inner_sum_many (with its step
-// list: tools/debug/inner_sum_check.cpp) and fhs_multiply_relin_many (with its chunk plan:
-// tools/debug/multiply_many_check.cpp), every table DevTables points
+// list: tools/debug/inner_sum_check.cpp), fhs_multiply_relin_many (with its chunk plan:
+// tools/debug/multiply_many_check.cpp) and fhs_weighted_sums (with its weight tables and chunk plan:
+// tools/debug/weighted_sums_check.cpp), every table DevTables points
 // to (as std::vectors, HostTables) and the constants of the decoder's CRT composition.  No HIP runtime
 // call: fhs_host.hip uploads what build_host_tables returns, and tools/debug/tables_check.cpp checks the
 // same tables with plain g++ (through tools/debug/shim) under the host sanitizers.
@@ -332,6 +333,89 @@ static std::vector<std::pair<int, int>> batch_chunks(int n, size_t item_bytes, i
         at += r;
     }
     return chunks;
+}
+
+// ============================================================================ fhs_weighted_sums (host side)
+// Two scales are one scale when they agree to 1e-9 relative (fhs_add's judgement).
+static bool scales_close(double a, double b) { return std::fabs(a - b) <= 1e-9 * std::max(std::fabs(a), std::fabs(b)); }
+constexpr int kWsumMaxF = 4096;               // inputs per call: the rounding sum stays below 2^72 (wsum_round_term)
+constexpr int kWsumMaxOutputs = kKsMaxItems;  // outputs per chunk
+enum WsumErr { WSUM_INVALID = 0, WSUM_LEVEL = 1, WSUM_SCALE = 2 };
+// The arguments of fhs_weighted_sums, from what the host layer reads off the F handles (component counts, chain
+// indices, scales).  The message of the first argument that is wrong, or null; *cls is its status class.
+static const char* weighted_sums_error(bool null_arg, int F, int E, int64_t ldw, double scale, const int* ncomp,
+                                       const int* ci, const double* scales, int L0, WsumErr* cls) {
+    *cls = WSUM_INVALID;
+    if (null_arg) return "null argument";
+    if (F < 1 || F > kWsumMaxF) return "weighted_sums: 1 <= F <= 4096";
+    if (E < 1) return "weighted_sums: E >= 1";
+    if (ldw < (int64_t)E) return "weighted_sums: ldw >= E";
+    if (!(scale > 0) || !std::isfinite(scale)) return "weighted_sums: bad scale";
+    if (!ncomp || !ci || !scales) return "null argument";
+    for (int j = 0; j < F; ++j)
+        if (ncomp[j] != 2) return "weighted_sums expects 2-component ciphertexts";
+    *cls = WSUM_LEVEL;
+    for (int j = 1; j < F; ++j)
+        if (ci[j] != ci[0]) return "weighted_sums: inputs must share one chain index";
+    if (ci[0] < 1 || ci[0] > L0) return "chain index out of range";
+    if (L0 + 1 - ci[0] < 2) return "rescale_to_next: no level left (end of modulus switching chain)";
+    *cls = WSUM_SCALE;
+    for (int j = 1; j < F; ++j)
+        if (!scales_close(scales[j], scales[0])) return "scale mismatch";
+    *cls = WSUM_INVALID;
+    return nullptr;
+}
+// The weight tables of one call at l limbs (L = l - 1, the limb the rescale drops): the plaintext of (output i, input j)
+// is the constant c_ij = round(W[j ldw + i] scale), half away from zero as fhs_multiply_const rounds, k_ijm = c_ij mod q_m.
+//   wl [2][F][Epad]      k_ijL and its Shoup word                              (the rounding sum's weights)
+//   wt [L][F + 1][Epad]  pack30(k_ijm inv_m mod q_m), inv_m = q_L^-1 mod q_m;  row F: pack30(q_m - inv_m), the weight
+//                        of the NTT'd rounding sum
+// Rows are Epad = E rounded up to the tile, plus one tile, words long (a chunk may start inside a tile; the padding
+// is zero).  Returns an error message (a weight not finite, or |c_ij| >= 2^62), or null.
+struct WsumTables {
+    int Epad = 0;
+    std::vector<uint64_t> wl, wt;
+};
+static const char* weighted_sums_tables(const double* W, int64_t ldw, int F, int E, double scale, const uint64_t* q, int l,
+                                        int tile, WsumTables& Wt) {
+    const int L = l - 1;
+    const size_t Epad = Wt.Epad = (E + tile - 1) / tile * tile + tile;
+    Wt.wl.assign((size_t)2 * F * Epad, 0);
+    Wt.wt.assign((size_t)L * (F + 1) * Epad, 0);
+    const uint64_t qL = q[L];
+    std::vector<uint64_t> inv(L), inv_s(L);
+    for (int m = 0; m < L; ++m) {
+        inv[m] = h_inv(qL % q[m], q[m]);
+        inv_s[m] = h_shoup(inv[m], q[m]);
+        for (int i = 0; i < E; ++i) Wt.wt[((size_t)m * (F + 1) + F) * Epad + i] = pack30(q[m] - inv[m]);
+    }
+    for (int j = 0; j < F; ++j)
+        for (int i = 0; i < E; ++i) {
+            const double p = std::round(W[(size_t)j * ldw + i] * scale);
+            if (!std::isfinite(p)) return "weighted_sums: a weight is not finite";
+            if (!(std::fabs(p) < 4611686018427387904.0)) return "weighted_sums: |weight x scale| >= 2^62";
+            const int64_t c = (int64_t)p;
+            const uint64_t mag = c < 0 ? (uint64_t)0 - (uint64_t)c : (uint64_t)c;
+            auto res = [&](uint64_t m) {
+                const uint64_t r = mag % m;
+                return c < 0 && r ? m - r : r;
+            };
+            const uint64_t kL = res(qL);
+            Wt.wl[(size_t)j * Epad + i] = kL;
+            Wt.wl[((size_t)F + j) * Epad + i] = h_shoup(kL, qL);
+            for (int m = 0; m < L; ++m)
+                Wt.wt[((size_t)m * (F + 1) + j) * Epad + i] = pack30(shoup_hd(res(q[m]), inv[m], inv_s[m], q[m]));
+        }
+    return nullptr;
+}
+// The chunks over the E outputs: per output the rounding sums (2 components x 2 words per coefficient) and their NTT'd
+// residues (2 (l - 1) N words); once per call the inputs' coefficient-form last limbs (2 F N words), which come off
+// the cap (kMulManyCap, as fhs_multiply_relin_many).  At fri's ring (N = 32768, l = 9, F = 256) that is 5.2 MB per
+// output and 134 MB once: a chunk is at most 179 outputs.
+static size_t weighted_sums_item_bytes(size_t N, int l) { return 8 * N * (4 + 2 * (size_t)(l - 1)); }
+static std::vector<std::pair<int, int>> weighted_sums_chunks(int E, int F, size_t N, int l, size_t cap = kMulManyCap) {
+    const size_t fixed = 16 * (size_t)F * N;
+    return batch_chunks(E, weighted_sums_item_bytes(N, l), kWsumMaxOutputs, cap > fixed ? cap - fixed : 0);
 }
 
 // ============================================================================ parameter tables

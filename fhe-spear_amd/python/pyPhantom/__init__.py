@@ -169,6 +169,9 @@ _SIGS = {
     "fhs_bsgs_giant_steps_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, _u64p, _vp, C.POINTER(_vp)]),
     "fhs_linear_transform": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, C.c_int, _u64p, _vp,
                                        C.c_int, C.POINTER(_vp)]),
+    "fhs_weighted_sums": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _dblp, C.c_int64, C.c_int, C.c_double, C.POINTER(_vp)]),
+    "fhs_debug_wsum_round": (C.c_int, [_u64, _u64p, _u64p, C.c_int, C.POINTER(C.c_int64), _u64p]),
+    "fhs_debug_wsum_accumulate": (C.c_int, [_u64, _u64p, _u64p, C.c_int, _u64, _u64, _u64p]),
     "fhs_multiply_const": (C.c_int, [_vp, _vp, C.c_double, C.c_double, C.POINTER(_vp)]),
     "fhs_add_const": (C.c_int, [_vp, _vp, C.c_double, C.POINTER(_vp)]),
     "fhs_mod_raise": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -1026,6 +1029,32 @@ def multiply_relin_many(ctx, a, b, rk, rescale=True):
     return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
 
 
+def weighted_sums(ctx, cts, W, scale):
+    """Extension: out[i] = sum_j rescale_to_next(multiply_plain(cts[j], P_ij)) for every output column i at once
+    (fhs_weighted_sums) -- the reference's ct_pt_weighted_sum (fhe_rwkv_inference.py:79-94) per column, limb-identical
+    to its loop (every term rescaled on its own, then added) in a constant number of launches.  W: an (F, E) array
+    of weights, F = len(cts); P_ij is the constant plaintext round(W[j, i] * scale) at the inputs' chain index.
+    Returns E ciphertexts at chain index + 1 that share one device block."""
+    cts = list(cts)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    if W.ndim != 2 or W.shape[0] != len(cts):
+        raise ValueError(f"weighted_sums: W must be an (F, E) array with F = {len(cts)} rows, got shape {W.shape}")
+    F, E = W.shape
+    ins = (_vp * max(F, 1))(*[c._h for c in cts])
+    outs = (_vp * max(E, 1))()
+    buf = W if W.size else np.zeros(1)               # an empty array may have no address: F, E are what is wrong
+    _check(_lib.fhs_weighted_sums(ctx._h, ins, F, buf.ctypes.data_as(_dblp), E, E, float(scale), outs), "weighted_sums")
+    return [ciphertext(ctx, _vp(outs[i])) for i in range(E)]
+
+
+def weighted_sum(ctx, cts, weights, scale):
+    """The E = 1 case of weighted_sums: sum_j rescale_to_next(multiply_plain(cts[j], const(weights[j])))."""
+    w = np.asarray(weights, dtype=np.float64)
+    if w.ndim != 1:
+        raise ValueError(f"weighted_sum: weights must be one-dimensional, got shape {w.shape}")
+    return weighted_sums(ctx, cts, w.reshape(-1, 1), scale)[0]
+
+
 def square_many(ctx, cts, rk, rescale=True):
     """Extension: the reference's ct_ct_square (fhe_rwkv_inference.py:97-101) for every ciphertext of `cts` in one
     call: multiply_relin_many with b = a, whose tensor kernel then reads each operand once."""
@@ -1245,11 +1274,14 @@ class Event:
 KERNEL_IDS = {"k_bsgs_inner": 0, "k_modup": 1, "k_ks_ip": 2, "k_moddown": 3, "k_ks_intt": 4,
               "k_ks_special_intt": 5, "k_giant_sum": 6, "k_giant_final": 7, "rescale": 8, "k_dot_tensor": 9,
               "encrypt_pk": 10}
+# the stages of weighted_sums (fhs::KID_WSUM_*), armed and read by the same two calls
+STAGE_IDS = {"wsum_intt": 11, "wsum_round": 12, "wsum_encode": 13, "wsum_acc": 14}
 
 
 def kernel_timer_arm(ctx, names=None):
     """Record HIP events around every launch of the named kernels (None = all, [] = off)."""
-    ids = KERNEL_IDS.values() if names is None else [KERNEL_IDS[n] for n in names]
+    both = {**KERNEL_IDS, **STAGE_IDS}
+    ids = KERNEL_IDS.values() if names is None else [both[n] for n in names]
     mask = 0
     for i in ids:
         mask |= 1 << i
@@ -1260,6 +1292,18 @@ def kernel_timer_read(ctx, reset=False):
     """{kernel: (ms, launches)} accumulated since the last reset."""
     out = {}
     for name, kid in KERNEL_IDS.items():
+        ms, n = C.c_float(), C.c_int()
+        _check(_lib.fhs_kernel_timer(ctx._h, kid, C.byref(ms), C.byref(n), 0), "kernel_timer")
+        out[name] = (float(ms.value), int(n.value))
+    if reset:
+        _check(_lib.fhs_kernel_timer(ctx._h, -1, None, None, 1), "kernel_timer")
+    return out
+
+
+def stage_timer_read(ctx, reset=False):
+    """{stage: (ms, launches)} of the weighted_sums stages armed by name with kernel_timer_arm (STAGE_IDS)."""
+    out = {}
+    for name, kid in STAGE_IDS.items():
         ms, n = C.c_float(), C.c_int()
         _check(_lib.fhs_kernel_timer(ctx._h, kid, C.byref(ms), C.byref(n), 0), "kernel_timer")
         out[name] = (float(ms.value), int(n.value))

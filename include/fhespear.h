@@ -357,6 +357,25 @@ fhs_status fhs_dot_product_many(fhs_context* ctx, const fhs_ciphertext* const* q
 fhs_status fhs_multiply_relin_many(fhs_context* ctx, const fhs_ciphertext* const* a,
                                    const fhs_ciphertext* const* b, int n, const fhs_relin_key* rk,
                                    int rescale, fhs_ciphertext** out_array);
+/* Extension (fri:79-94, ct_pt_weighted_sum for every output column at once):
+ *   out_array[i] = sum_{j<F} rescale_to_next( multiply_plain( in[j], P_ij ) ),   i < E
+ * P_ij: the plaintext at in's chain index and scale `scale` whose every slot is W[j*ldw + i].
+ * Limb-identical to the reference's loop -- every term rescaled on its own, then added (not "sum, then one rescale",
+ * which gives other limbs) -- in a constant number of launches per chunk of outputs, whatever F and E.  P_ij is the
+ * constant polynomial c_ij = round(W[j*ldw + i] * scale), half away from zero (fhs_multiply_const's rounding); its NTT
+ * image is c_ij mod q_m in every position of limb m, which is what an exact encoder gives for a constant vector.  The
+ * GPU's float64 encoder (fhs_encode*) can differ from it where W * scale lies within its FFT error of a half-integer.
+ * Result i has scale in.scale * scale / q_{l-1} and chain index + 1.  Inputs have 2 components (else
+ * FHS_ERR_INVALID), share one chain index (else FHS_ERR_LEVEL) and one scale as fhs_add judges it (else
+ * FHS_ERR_SCALE); 1 <= F <= 4096, E >= 1, ldw >= E, `scale` finite and > 0, every weight finite with
+ * |c_ij| < 2^62 (else FHS_ERR_INVALID); at the last level the call is FHS_ERR_LEVEL.  A handle may appear several
+ * times in `in`.  Queued rotation outputs used as inputs are flushed first; a lost input is rejected.  The inputs are
+ * not written and may be destroyed as soon as the call returns.  Every allocation precedes the first launch; on
+ * failure nothing stays allocated and out_array is untouched.  Lifetime: the E results share one device block,
+ * returned to the cache when the LAST of them is destroyed. */
+fhs_status fhs_weighted_sums(fhs_context* ctx, const fhs_ciphertext* const* in, int F,
+                             const double* W, int64_t ldw, int E, double scale,
+                             fhs_ciphertext** out_array);
 /* Extension (no reference symbol): bg:198-203 + bg:361-432 on the device -- the D diagonals of the
  * D x D row-major matrix M1 (complex: M1 + i M2; M2 = NULL for real), group g = k / G rolled by g G,
  * tiled to N/2 slots, encoded at `scale` / `chain_index`.  Limb-identical to encode_*_vector_batch
@@ -443,6 +462,14 @@ fhs_status fhs_debug_moddown_xform(const uint64_t* p3, const uint64_t* y3, uint6
  * terms.  Operands must be < q. */
 fhs_status fhs_debug_dot_accumulate(uint64_t q, const uint64_t* a0, const uint64_t* a1, const uint64_t* b0,
                                     const uint64_t* b1, int J, uint64_t* out3);
+/* Test hooks: the per-coefficient routines of fhs_weighted_sums' two pointwise stages (the kernel's own
+ * __host__ __device__ routines) run on the host.  round: the rounding sum S = sum_j centre(k[j] d[j] mod qL),
+ * centre(u) = ((u + (qL >> 1)) mod qL) - (qL >> 1), as the signed 128-bit integer *hi 2^64 + *lo.  accumulate:
+ * *out = (sum_j kprime[j] c[j] + wT t) mod q with split-30 partial sums, Acc3 folds and one reduction per window of
+ * 64 products.  q odd and < 2^60, operands < q, 1 <= F <= 4096. */
+fhs_status fhs_debug_wsum_round(uint64_t qL, const uint64_t* k, const uint64_t* d, int F, int64_t* hi, uint64_t* lo);
+fhs_status fhs_debug_wsum_accumulate(uint64_t q, const uint64_t* kprime, const uint64_t* c, int F, uint64_t wT,
+                                     uint64_t t, uint64_t* out);
 
 #ifdef __cplusplus
 }
