@@ -41,9 +41,10 @@ KS_LEVELS = {"X59": (6, 5), "X60s": (6,), "S59": (4,), "S60": (4,)}
 _SPLIT_WHY = ("ks_moddown_stage selects the SPLIT form only under `LOGN == 15 && nwg < FHS_SPLIT_MAX_WG`; its "
               "function-pointer table instantiates it for every LOGN >= 9")
 EXEMPT = {f"k_moddown_h<{n}, true, true, true>": _SPLIT_WHY for n in range(9, 15)}
-EXEMPT["k_rescale_intt<14, true>"] = (
-    "launch_rescale: FHS_NTT_LAUNCH(k_rescale_intt, ncomp, ...) takes K<14, true> only from FHS_FULL_FORM_MAX_WG = "
-    "256 workgroups, and ncomp <= 3")
+# Not exempt: k_rescale_intt<14, true> (FHS_NTT_LAUNCH from FHS_FULL_FORM_MAX_WG = 256 workgroups).  The single rescale
+# passes ncomp <= 3, but fhs_multiply_relin_many passes ocomp * R and fhs_dot_product_many ocomp * C components to
+# launch_rescale, and launch_last_limbs_intt (fhs_weighted_sums) 2 * F: 128 pairs, chunks or inputs at N = 16384
+# reach it.  case_multiply_many_at_128_pairs launches it.
 
 
 def logn_of(kernel):
@@ -154,6 +155,28 @@ def case_giant_final_at_128_limbs(ph, N, envs):
         same(pts[k].to_numpy(), pn[k], f"128 + 8: random plaintext {k}")
     y = ph.bsgs_multiply_accumulate(ctx, [up(ph, ctx, o, a)], pts, 1, 2, 2, gk)
     same(y.to_numpy(), o.bsgs_loop([a], pn, [None, okey], 1, 2, 2), "128 + 8: bsgs_multiply_accumulate")
+
+
+def case_multiply_many_at_128_pairs(ph, N, envs):
+    """N = 16384 only: multiply_relin_many of 128 pairs on [60, 40, 40, 60], P = 1 at l = 2 (pair i is (x_i, x_{i+1})).
+    Its rescale is one launch_rescale over 2 * 128 = 256 components: k_rescale_intt<14, true> (and, (l - 1) * 256
+    workgroups, k_rescale_ntt<14, true>) into the 128 results' block.  tests/test_batched_rings.py runs both sides of
+    this threshold with the ledger's names asserted."""
+    if N != 16384:
+        return
+    n, l, seed = 128, 2, SEED + 2
+    ctx, sk, o = make_ctx(ph, N, [60, 40, 40, 60], 1, steps=(1,), seed=seed)
+    s = o.gen_secret(seed)
+    same(sk.export(), s, "128 pairs: secret key")
+    rlk, orlk = sk.gen_relinkey(ctx), o.gen_relin_key(seed, s)
+    rng = np.random.default_rng(N + n)
+    xs = [rand_ct(o, rng, 2, l) for _ in range(n + 1)]
+    cts = [up(ph, ctx, o, a) for a in xs]
+    outs = ph.multiply_relin_many(ctx, cts[:n], cts[1:], rlk)
+    assert len(outs) == n
+    for i, out in enumerate(outs):
+        assert out.size() == 2 and out.chain_index() == o.L0 + 2 - l
+        same(out.to_numpy(), o.rescale(o.relinearize(o.multiply(xs[i], xs[i + 1]), orlk)), f"128 pairs: pair {i}")
 
 
 def case_seal(ph, N, envs):
@@ -313,8 +336,8 @@ def case_encode_unfused(N, ring, tmp_path):
     return set(ledger[0])
 
 
-RING_CASES = [case_keyswitch_selectors, case_keyswitch_batch, case_bsgs, case_giant_final_at_128_limbs, case_seal,
-              case_rescale, case_encode, case_client]
+RING_CASES = [case_keyswitch_selectors, case_keyswitch_batch, case_bsgs, case_giant_final_at_128_limbs,
+              case_multiply_many_at_128_pairs, case_seal, case_rescale, case_encode, case_client]
 
 
 def shared_contexts(ph, orc, N):

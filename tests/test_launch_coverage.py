@@ -5,7 +5,7 @@ which kernels were launched.  tests/golden/kernel_manifest.json lists every kern
 below: the committed list equals the library's, so adding or removing an instantiation means regenerating it with
 tests/golden/make_kernel_manifest.py).  One GPU test per ring then arms the ledger, runs that ring's cases of
 tests/_launch_matrix.py -- each comparing what the library returned -- and asserts that every manifest kernel of the
-ring was launched or is in EXEMPT (the 7 instantiations no argument can launch), and that no EXEMPT kernel was
+ring was launched or is in EXEMPT (the 6 instantiations no argument can launch), and that no EXEMPT kernel was
 launched.  A kernel added later without such a case fails its ring's test by name."""
 import ctypes
 import json
