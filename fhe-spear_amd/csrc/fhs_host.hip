@@ -183,7 +183,7 @@ struct fhs_context {
     uint64_t* scr[SCR_COUNT] = {};
     size_t scr_bytes[SCR_COUNT] = {};
     static constexpr int kMaxItems = kKsMaxItems;
-    static constexpr int kMaxPtrs = 1 << 16;
+    static constexpr int kMaxPtrs = kStagedMaxPtrs;
 };
 
 struct fhs_ciphertext {
@@ -3163,6 +3163,70 @@ extern "C" fhs_status fhs_multiply_relin_many(fhs_context* c, const fhs_cipherte
                                          ws, wsb, c->items_dev, c->stager, c->st, tm), "key-switch");
         }
         if (rescale) HIPCHK(fhs::launch_rescale(c->T, rk ? relin : t3, slice, scr, ocomp * R, l, c->st, tm), "rescale");
+    }
+    std::copy(cts.begin(), cts.end(), out_array);
+    return bo.keep(FHS_OK);
+}
+
+// ============================================================================ batched CT x PT multiply and rescale
+// out[i] = rescale_to_next(multiply_plain(a[i], p[i])) for n pairs (fri:67-70, the head of ct_pt_dot for every column
+// at once; p null: the rescale alone), limb-identical to the two calls per pair.  Per chunk of R pairs (fhs_tables.h
+// mulp_rescale_chunks) the two launches of ONE rescale over the 2 R components (launch_rescale_many), which read the
+// operands through staged pointer lists and form each product in their loads: no product is stored.  The second
+// launch writes the chunk's slice of the results' block (new_cts), which is exactly its [R][2][l - 1][N] layout.
+extern "C" fhs_status fhs_multiply_plain_rescale_many(fhs_context* c, const fhs_ciphertext* const* a,
+                                                      const fhs_plaintext* const* p, int n, fhs_ciphertext** out_array) {
+    ENTER(c);
+    const bool null_arg = !a || !out_array;
+    const int cnt = (null_arg || n < 1) ? 0 : n;
+    std::vector<int> ncomp(cnt), cis(cnt), pcis(p ? cnt : 0);
+    for (int k = 0; k < cnt; ++k) {
+        if (!a[k] || (p && !p[k])) return fail(FHS_ERR_INVALID, "null argument");
+        LIVE(a[k]);
+        ncomp[k] = a[k]->ncomp;
+        cis[k] = a[k]->ci;
+        if (p) pcis[k] = p[k]->ci;
+    }
+    bool level = false;
+    if (const char* bad = mulp_rescale_many_error(null_arg, n, ncomp.data(), cis.data(), p ? pcis.data() : nullptr, c->L0, &level))
+        return fail(level ? FHS_ERR_LEVEL : FHS_ERR_INVALID, bad);
+    const int ci = a[0]->ci, l = a[0]->l;
+    const size_t N = c->N;
+    const std::vector<std::pair<int, int>> chunks = mulp_rescale_chunks(n, N);
+    const size_t Rmax = (size_t)chunks[0].second;
+    // every allocation before the first launch of the call's own kernels; out_array is written only on success
+    uint64_t* scr = nullptr;
+    HIPCHK(scratch(c, fhs_context::SCR_RESCALE, mulp_rescale_item_bytes(N) * Rmax, &scr), "rescale");
+    std::vector<fhs_ciphertext*> held((size_t)n), cts;
+    BatchOutT<fhs_ciphertext> bo(held.data(), (size_t)n);
+    fhs_status s = new_cts(c, n, 2, ci + 1, 1.0, cts);
+    if (s != FHS_OK) return s;
+    std::copy(cts.begin(), cts.end(), held.begin());
+    std::vector<const uint64_t*> pd(p ? n : 0);
+    for (int i = 0; i < n; ++i) {
+        double sc = a[i]->scale;                       // fhs_multiply_plain's, then fhs_rescale_to_next's
+        if (p) {
+            sc = a[i]->scale * p[i]->scale;
+            HIPCHK(pt_dense(c, p[i], &pd[i]), "multiply_plain_rescale_many");   // a compact-only plaintext's dense limbs
+        }
+        cts[i]->scale = sc / (double)c->q[l - 1];
+    }
+    uint64_t* const res = cts[0]->d;   // [n][2][l - 1][N]: one block (new_cts), or the single ciphertext
+    const size_t per_out = 2 * (size_t)(l - 1) * N;
+    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    std::vector<const uint64_t*> ptrs;
+    for (const auto& ch : chunks) {
+        const int i0 = ch.first, R = ch.second;
+        // the chunk's pointer lists, the ciphertexts' then the plaintexts', staged in stream order
+        ptrs.resize((size_t)R * (p ? 2 : 1));
+        for (int r = 0; r < R; ++r) {
+            ptrs[r] = a[i0 + r]->d;
+            if (p) ptrs[R + r] = pd[i0 + r];
+        }
+        HIPCHK(stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * ptrs.size()), "multiply_plain_rescale_many");
+        const uint64_t* const* da = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
+        HIPCHK(fhs::launch_rescale_many(c->T, da, p ? da + R : nullptr, R, l, res + (size_t)i0 * per_out, scr, c->st, tm),
+               "multiply_plain_rescale_many");
     }
     std::copy(cts.begin(), cts.end(), out_array);
     return bo.keep(FHS_OK);

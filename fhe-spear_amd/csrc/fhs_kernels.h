@@ -132,6 +132,12 @@ hipError_t launch_tensor(const DevTables& T, const u64* const* a_dev, const u64*
                          int R, u64* out3, int l, hipStream_t st);
 hipError_t launch_rescale(const DevTables& T, const u64* in, u64* out, u64* scratch, int ncomp, int l,
                           hipStream_t st, const KTimer* tm = nullptr);
+// out[j] = rescale(ins_dev[j] * mul_dev[j]) for j < count (fri:67-70 per column), the plaintext product folded into
+// the loads of the rescale's two kernels: ins_dev / mul_dev are device pointer lists of 2-component ciphertexts and
+// of plaintexts at l limbs (mul_dev null: the rescale alone), out is [count][2][l - 1][N], scratch 2 count N words;
+// 2 count <= 65535.  Bracketed by KID_RESCALE.
+hipError_t launch_rescale_many(const DevTables& T, const u64* const* ins_dev, const u64* const* mul_dev, int count, int l,
+                               u64* out, u64* scratch, hipStream_t st, const KTimer* tm = nullptr);
 // Stream-ordered host->device copy of small launch descriptors (item lists, pointer arrays).  The
 // host side stages through pinned memory so the copy never blocks the calling thread on the GPU
 // queue; `src` may be reused as soon as the call returns.

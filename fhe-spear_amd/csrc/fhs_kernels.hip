@@ -609,23 +609,33 @@ hipError_t launch_galois_perm(const DevTables& T, const u64* in, u64* out, int l
 // ============================================================================ rescale (pb:185)
 // 1) last limb of each component -> coefficient form (scratch[comp])
 template <int LOGN, bool H = ntt_half<LOGN>()>
-__global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_rescale_intt(DevTables T, const u64* in, const u64* const* ins, u64* scratch, int l) {
+__global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_rescale_intt(DevTables T, const u64* in, const u64* const* ins,
+                                                                      const u64* const* mul, u64* scratch, int l) {
     constexpr int N = 1 << LOGN;
     __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, H>()];
     const int comp = blockIdx.x, pi = l - 1;
     const PrimeK& P = PK(T, pi);
-    // the components of one polynomial array, or (ins: fhs_weighted_sums) the two of each listed ciphertext
+    // the components of one polynomial array, or (ins: fhs_weighted_sums, fhs_multiply_plain_rescale_many) the two of
+    // each listed ciphertext
     const u64* src = ins ? ins[comp >> 1] + ((size_t)(comp & 1) * l + pi) * N : in + ((size_t)comp * l + pi) * N;
     u64* dst = scratch + (size_t)comp * N;
     const u64 half = P.q >> 1, q = P.q;
-    inv_limb<LOGN, FHS_NTT_RL, H>(lds, threadIdx.x, T.tw_inv + (size_t)pi * N * 2, q, P.ninv, P.ninv_s, P.w1ninv,
-                               P.w1ninv_s, [&](int e) { return src[e]; },
-                               [&](int e, u64 v) { dst[e] = addmod(v, half, q); });
+    const u64* tw = T.tw_inv + (size_t)pi * N * 2;
+    auto store = [&](int e, u64 v) { dst[e] = addmod(v, half, q); };
+    if (mul) {   // (mul: with ins) the product with the listed plaintext's last limb, k_eltwise's OP_MULP, never stored
+        const u64* pt = mul[comp >> 1] + (size_t)pi * N;
+        inv_limb<LOGN, FHS_NTT_RL, H>(lds, threadIdx.x, tw, q, P.ninv, P.ninv_s, P.w1ninv, P.w1ninv_s,
+                                   [&](int e) { return mulmod(src[e], pt[e], P); }, store);
+    } else {
+        inv_limb<LOGN, FHS_NTT_RL, H>(lds, threadIdx.x, tw, q, P.ninv, P.ninv_s, P.w1ninv, P.w1ninv_s,
+                                   [&](int e) { return src[e]; }, store);
+    }
 }
 // 2) per (i < l-1, comp): NTT_i([v mod q_i] - [half mod q_i]) and combine (a_i - t) * q_last^-1
 template <int LOGN, bool H = ntt_half<LOGN>()>
-__global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_rescale_ntt(DevTables T, const u64* in, const u64* scratch,
-                                                                     u64* out, int l) {
+__global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_rescale_ntt(DevTables T, const u64* in, const u64* const* ins,
+                                                                     const u64* const* mul, const u64* scratch, u64* out,
+                                                                     int l) {
     constexpr int N = 1 << LOGN;
     __shared__ __attribute__((aligned(16))) u64 lds[ntt_lds_words<LOGN, H>()];
     const int i = blockIdx.x, comp = blockIdx.y;
@@ -634,11 +644,20 @@ __global__ void __launch_bounds__((ntt_threads<LOGN, H>())) k_rescale_ntt(DevTab
     const u64* rs = T.rescale + ((size_t)l * T.L0 + i) * 4;   // inv, inv_s, half mod q_i
     const u64 inv = rs[0], inv_s = rs[1], hq = rs[2], q = RU.q;
     const u64* src = scratch + (size_t)comp * N;
-    const u64* a = in + ((size_t)comp * l + i) * N;
+    // limb i of a component of one polynomial array, or (ins) of component comp & 1 of ciphertext ins[comp >> 1]
+    const u64* a = ins ? ins[comp >> 1] + ((size_t)(comp & 1) * l + i) * N : in + ((size_t)comp * l + i) * N;
     u64* o = out + ((size_t)comp * (l - 1) + i) * N;
-    fwd_limb<LOGN, FHS_NTT_RL, H>(lds, threadIdx.x, T.tw_fwd + (size_t)i * N * 2, RU,
-                               [&](int e) { return submod(reduce64(src[e], P), hq, q); },
-                               [&](int e, u64 t) { o[e] = shoup(submod(a[e], t, q), inv, inv_s, q); });
+    const u64* tw = T.tw_fwd + (size_t)i * N * 2;
+    auto load = [&](int e) { return submod(reduce64(src[e], P), hq, q); };
+    if (mul) {   // (mul: with ins) a_i is the product with the listed plaintext's limb i, as k_rescale_intt formed it
+        const u64* pt = mul[comp >> 1] + (size_t)i * N;
+        fwd_limb<LOGN, FHS_NTT_RL, H>(lds, threadIdx.x, tw, RU, load, [&](int e, u64 t) {
+            o[e] = shoup(submod(mulmod(a[e], pt[e], P), t, q), inv, inv_s, q);
+        });
+    } else {
+        fwd_limb<LOGN, FHS_NTT_RL, H>(lds, threadIdx.x, tw, RU, load,
+                                   [&](int e, u64 t) { o[e] = shoup(submod(a[e], t, q), inv, inv_s, q); });
+    }
 }
 // N = 32768: a rescale is two latency-bound launches (2 and 2 (l - 1) workgroups, each transforming a whole limb as
 // two halves in turn).  Here every half gets its own workgroup -- twice the workgroups, half the serial work each:
@@ -739,8 +758,28 @@ hipError_t launch_rescale(const DevTables& T, const u64* in, u64* out, u64* scra
                 break;
             }
         }
-        FHS_NTT_LAUNCH(k_rescale_intt, ncomp, dim3(ncomp), st, T, in, static_cast<const u64* const*>(nullptr), scratch, l);
-        FHS_NTT_LAUNCH(k_rescale_ntt, (l - 1) * ncomp, dim3(l - 1, ncomp), st, T, in, scratch, out, l);
+        constexpr const u64* const* none = nullptr;
+        FHS_NTT_LAUNCH(k_rescale_intt, ncomp, dim3(ncomp), st, T, in, none, none, scratch, l);
+        FHS_NTT_LAUNCH(k_rescale_ntt, (l - 1) * ncomp, dim3(l - 1, ncomp), st, T, in, none, none, scratch, out, l);
+    });
+    FHS_TMARK(tm, KID_RESCALE, 0, st);
+    return hipGetLastError();
+}
+
+// fhs_multiply_plain_rescale_many: out[j] = rescale(ins_dev[j] * mul_dev[j]) for `count` 2-component ciphertexts and
+// plaintexts (device pointer lists; mul_dev null: the rescale alone) in the two launches of a rescale over 2 count
+// components, the product formed in both kernels' loads and never stored.  out is [count][2][l - 1][N], scratch
+// 2 count N words.  Always the general pair: the launch forms (full / half limb) follow the workgroup counts as in
+// launch_rescale.
+hipError_t launch_rescale_many(const DevTables& T, const u64* const* ins_dev, const u64* const* mul_dev, int count, int l,
+                               u64* out, u64* scratch, hipStream_t st, const KTimer* tm) {
+    if (!ins_dev || count < 1 || 2 * (size_t)count > 65535 || l < 2 || l > 65536) return hipErrorInvalidValue;
+    const int ncomp = 2 * count;
+    FHS_TMARK(tm, KID_RESCALE, 1, st);
+    FHS_DISPATCH_LOGN(T.logN, {
+        constexpr const u64* none = nullptr;
+        FHS_NTT_LAUNCH(k_rescale_intt, ncomp, dim3(ncomp), st, T, none, ins_dev, mul_dev, scratch, l);
+        FHS_NTT_LAUNCH(k_rescale_ntt, (l - 1) * ncomp, dim3(l - 1, ncomp), st, T, none, ins_dev, mul_dev, scratch, out, l);
     });
     FHS_TMARK(tm, KID_RESCALE, 0, st);
     return hipGetLastError();
@@ -753,7 +792,8 @@ hipError_t launch_last_limbs_intt(const DevTables& T, const u64* const* ins_dev,
     if (count < 1 || count > 65535 || l < 1) return hipErrorInvalidValue;
     FHS_TMARK(tm, KID_WSUM_INTT, 1, st);
     FHS_DISPATCH_LOGN(T.logN, {
-        FHS_NTT_LAUNCH(k_rescale_intt, 2 * count, dim3(2 * count), st, T, static_cast<const u64*>(nullptr), ins_dev, dco, l);
+        FHS_NTT_LAUNCH(k_rescale_intt, 2 * count, dim3(2 * count), st, T, static_cast<const u64*>(nullptr), ins_dev,
+                       static_cast<const u64* const*>(nullptr), dco, l);
     });
     FHS_TMARK(tm, KID_WSUM_INTT, 0, st);
     return hipGetLastError();

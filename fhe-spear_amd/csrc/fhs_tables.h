@@ -1,7 +1,8 @@
 // fhs_tables.h -- host-only derivation of a context's parameter tables: the host number theory, the
 // coefficient-modulus search, argument validation for fhs_context_create and fhs_inner_sum_many (with its step
 // list: tools/debug/inner_sum_check.cpp), fhs_multiply_relin_many (with its chunk plan:
-// tools/debug/multiply_many_check.cpp) and fhs_weighted_sums (with its weight tables and chunk plan:
+// tools/debug/multiply_many_check.cpp), fhs_multiply_plain_rescale_many (with its chunk plan:
+// tools/debug/mulp_rescale_check.cpp) and fhs_weighted_sums (with its weight tables and chunk plan:
 // tools/debug/weighted_sums_check.cpp), every table DevTables points
 // to (as std::vectors, HostTables) and the constants of the decoder's CRT composition.  No HIP runtime
 // call: fhs_host.hip uploads what build_host_tables returns, and tools/debug/tables_check.cpp checks the
@@ -333,6 +334,43 @@ static std::vector<std::pair<int, int>> batch_chunks(int n, size_t item_bytes, i
         at += r;
     }
     return chunks;
+}
+
+// ============================================================================ fhs_multiply_plain_rescale_many (host side)
+// The arguments of fhs_multiply_plain_rescale_many, from what the host layer reads off the handles: the n
+// ciphertexts' component counts and chain indices and (pci non-null: the call has plaintexts) the n plaintexts' chain
+// indices.  The message of the first argument that is wrong, or null; *level is set when that argument is a level
+// error (FHS_ERR_LEVEL) rather than an invalid one.
+static const char* mulp_rescale_many_error(bool null_arg, int n, const int* ncomp, const int* ci, const int* pci, int L0,
+                                           bool* level) {
+    *level = false;
+    if (null_arg) return "null argument";
+    if (n < 1) return "multiply_plain_rescale_many: n >= 1";
+    if (!ncomp || !ci) return "null argument";
+    for (int k = 0; k < n; ++k)
+        if (ncomp[k] != 2) return "multiply_plain_rescale_many expects 2-component ciphertexts";
+    *level = true;
+    for (int k = 1; k < n; ++k)
+        if (ci[k] != ci[0]) return "multiply_plain_rescale_many: inputs must share one chain index";
+    for (int k = 0; pci && k < n; ++k)
+        if (pci[k] != ci[0]) return "ciphertext and plaintext are at different chain indices";
+    if (ci[0] < 1 || ci[0] > L0) return "chain index out of range";
+    if (L0 + 1 - ci[0] < 2) return "rescale_to_next: no level left (end of modulus switching chain)";
+    *level = false;
+    return nullptr;
+}
+// The chunks of one call over n items at ring size N.  An item is one (ciphertext, plaintext) pair: two staged device
+// pointers, two workgroups of the rescale's first launch and 2 (l - 1) of its second (grid.y = 2 items), and the two
+// components' last limbs in coefficient form, 16 N bytes of the grow-only rescale scratch (8 MB per 16 columns at
+// N = 32768; the cap kMulManyCap is never the bound below N = 2^17).  So a chunk is bound by the item buffer's length
+// (the batch bound of every batched entry), by the staged pointer buffer and by the grid limit; the first is the
+// tightest today and all three are stated so that none is assumed.
+constexpr int kStagedMaxPtrs = 1 << 16;   // the context's staged pointer buffer holds 2 x this many pointers
+constexpr int kGridMaxY = 65535;
+constexpr int kMulpRescaleMaxItems = std::min(kKsMaxItems, std::min(kStagedMaxPtrs, kGridMaxY / 2));
+static size_t mulp_rescale_item_bytes(size_t N) { return 16 * N; }
+static std::vector<std::pair<int, int>> mulp_rescale_chunks(int n, size_t N, size_t cap = kMulManyCap) {
+    return batch_chunks(n, mulp_rescale_item_bytes(N), kMulpRescaleMaxItems, cap);
 }
 
 // ============================================================================ fhs_weighted_sums (host side)

@@ -164,6 +164,7 @@ _SIGS = {
     "fhs_dot_product_many": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _vp, C.c_int,
                                        C.POINTER(_vp)]),
     "fhs_multiply_relin_many": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
+    "fhs_multiply_plain_rescale_many": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.POINTER(_vp)]),
     "fhs_bsgs_giant_steps":(C.c_int, [_vp, C.POINTER(_vp), C.c_int, _u64p, _vp, C.POINTER(_vp)]),
     "fhs_bsgs_inner_products_device": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.c_int, _vp]),
     "fhs_bsgs_giant_steps_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, _u64p, _vp, C.POINTER(_vp)]),
@@ -924,8 +925,56 @@ def ct_pt_dot_many(ctx, ct, pts, dim, gk):
     """Extension: the reference's ct_pt_dot (fhe_rwkv_inference.py:66-76) for every plaintext of `pts` --
     rescale_to_next(multiply_plain(ct, pt)) per column, then ONE inner_sum_many over all columns, limb-identical
     to the per-column calls."""
-    prods = [rescale_to_next(ctx, multiply_plain(ctx, ct, p)) for p in pts]
-    return inner_sum_many(ctx, prods, dim, gk)
+    return inner_sum_many(ctx, multiply_plain_rescale_many(ctx, ct, list(pts)), dim, gk)
+
+
+def multiply_plain_rescale_many(ctx, cts, pts):
+    """Extension: rescale_to_next(multiply_plain(cts[i], pts[i])) for every pair at once
+    (fhs_multiply_plain_rescale_many) -- the head of the reference's ct_pt_dot (fhe_rwkv_inference.py:67-70) per
+    column, limb-identical to the two calls per pair, in two launches per chunk of pairs: the product is formed inside
+    the rescale's kernels and never stored.  cts: a list, or ONE ciphertext used for every plaintext.  pts=None
+    rescales alone (see rescale_many).  Ciphertexts and plaintexts share one chain index, their scales may differ.
+    The results share one device block."""
+    if pts is not None:
+        pts = list(pts)
+    if isinstance(cts, ciphertext):
+        cts = [cts] * (1 if pts is None else len(pts))
+    cts = list(cts)
+    n = len(cts)
+    pp = None
+    if pts is not None:
+        if len(pts) != n:
+            raise ValueError(f"multiply_plain_rescale_many: lists of different length ({n} and {len(pts)})")
+        pp = (_vp * max(n, 1))(*[p._h for p in pts])
+    aa = (_vp * max(n, 1))(*[c._h for c in cts])
+    outs = (_vp * max(n, 1))()
+    _check(_lib.fhs_multiply_plain_rescale_many(ctx._h, aa, pp, n, outs), "multiply_plain_rescale_many")
+    return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+
+
+def rescale_many(ctx, cts):
+    """Extension: rescale_to_next of every ciphertext of `cts` in one call (two launches per chunk), limb-identical
+    to the single calls: multiply_plain_rescale_many without plaintexts."""
+    return multiply_plain_rescale_many(ctx, list(cts), None)
+
+
+def ct_pt_dot_columns(ctx, ct, W, dim, scale, gk):
+    """Extension: the reference's ct_pt_dot (fhe_rwkv_inference.py:66-76) for every column of the (dim, F) array W --
+    the F columns, zero-padded to the slot count as fri:67-68 pads them, encoded by ONE encode_double_vector_batch at
+    ct's chain index, then ONE multiply_plain_rescale_many and ONE inner_sum_many.  Returns F ciphertexts whose
+    slot 0 holds the dot product of ct's first `dim` slots with the column."""
+    W = np.asarray(W, dtype=np.float64)
+    dim = int(dim)
+    if W.ndim != 2 or W.shape[0] != dim:
+        raise ValueError(f"ct_pt_dot_columns: W must be a (dim, F) array with dim = {dim} rows, got shape {W.shape}")
+    enc = ckks_encoder(ctx)
+    slots = enc.slot_count()
+    if dim > slots:
+        raise ValueError(f"ct_pt_dot_columns: dim {dim} exceeds the {slots} slots")
+    mat = np.zeros((W.shape[1], slots), dtype=np.float64)
+    mat[:, :dim] = W.T
+    pts = enc.encode_double_vector_batch(ctx, mat, float(scale), chain_index=ct.chain_index())
+    return inner_sum_many(ctx, multiply_plain_rescale_many(ctx, ct, pts), dim, gk)
 
 
 def bsgs_multiply_accumulate(ctx, ct_baby, pts, G, B, D, gk):
@@ -1067,7 +1116,7 @@ def dot_product_plain_many(ctx, query, pt_chunks, rescale=True):
     (bsgs_inner_products with the query as the baby steps and one "giant group" per chunk)."""
     J, Cn = _chunk_rows("dot_product_plain_many", query, pt_chunks)
     sums = bsgs_inner_products(ctx, list(query), [p for row in pt_chunks for p in row], J, Cn)
-    return [rescale_to_next(ctx, s) for s in sums] if rescale else sums
+    return rescale_many(ctx, sums) if rescale else sums
 
 
 # ------------------------------------------------------------------ bootstrapping primitives

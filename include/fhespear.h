@@ -357,6 +357,19 @@ fhs_status fhs_dot_product_many(fhs_context* ctx, const fhs_ciphertext* const* q
 fhs_status fhs_multiply_relin_many(fhs_context* ctx, const fhs_ciphertext* const* a,
                                    const fhs_ciphertext* const* b, int n, const fhs_relin_key* rk,
                                    int rescale, fhs_ciphertext** out_array);
+/* Extension (fri:67-70 for every column at once): out_array[i] = rescale_to_next( multiply_plain( a[i], p[i] ) ), i < n,
+ * limb-identical to the two calls per pair, in two launches per chunk with no product stored.
+ * p = NULL: out_array[i] = rescale_to_next( a[i] ).
+ * n >= 1; every a[i] has 2 components (else FHS_ERR_INVALID); all a[i] and p[i] share one chain index (else
+ * FHS_ERR_LEVEL); at the last level the call is FHS_ERR_LEVEL.  A handle may appear any number of times in a or p
+ * (ct_pt_dot passes one ciphertext n times).  Output i has scale a[i].scale * p[i].scale / q_{l-1} (p = NULL:
+ * a[i].scale / q_{l-1}), computed as the two single calls compute it, and chain index + 1.  Queued rotation outputs
+ * used as inputs are flushed first; a lost input is rejected; a compact-only plaintext gets its dense limbs first.
+ * Every allocation precedes the first launch of the call's own kernels; on failure nothing stays allocated and
+ * out_array is untouched.  The inputs are not written and may be destroyed as soon as the call returns.  Lifetime: the
+ * n results share one device block, returned to the cache when the LAST of them is destroyed. */
+fhs_status fhs_multiply_plain_rescale_many(fhs_context* ctx, const fhs_ciphertext* const* a,
+                                           const fhs_plaintext* const* p, int n, fhs_ciphertext** out_array);
 /* Extension (fri:79-94, ct_pt_weighted_sum for every output column at once):
  *   out_array[i] = sum_{j<F} rescale_to_next( multiply_plain( in[j], P_ij ) ),   i < E
  * P_ij: the plaintext at in's chain index and scale `scale` whose every slot is W[j*ldw + i].
