@@ -577,6 +577,28 @@ static fhs_status new_cts(fhs_context* c, int count, int ncomp, int ci, double s
     }
     return FHS_OK;
 }
+// The batch counterpart of Ct: n new ciphertexts in one device block (new_cts) on their way to the caller, destroyed
+// -- the block back to the cache -- unless committed, so the caller's array is written on success and only then.
+// make() is new_cts: nothing is held when it fails.
+struct CtBlock {
+    fhs_context* c;
+    std::vector<fhs_ciphertext*> cts;
+    explicit CtBlock(fhs_context* c_) : c(c_) {}
+    CtBlock(const CtBlock&) = delete;
+    CtBlock& operator=(const CtBlock&) = delete;
+    ~CtBlock() {
+        for (fhs_ciphertext* ct : cts) destroy_obj(ct);
+    }
+    fhs_status make(int n, int ncomp, int ci, double scale) { return new_cts(c, n, ncomp, ci, scale, cts); }
+    fhs_ciphertext* operator[](size_t i) const { return cts[i]; }
+    uint64_t* base() const { return cts[0]->d; }   // [n][ncomp][l][N]: one block, or the single ciphertext
+    size_t words_per_ct() const { return (size_t)cts[0]->ncomp * cts[0]->l * c->N; }
+    fhs_status commit(fhs_ciphertext** out) {
+        std::copy(cts.begin(), cts.end(), out);
+        cts.clear();
+        return FHS_OK;
+    }
+};
 static size_t ct_bytes(const fhs_ciphertext* ct) { return 8ull * ct->ncomp * ct->l * ct->ctx->N; }
 static size_t pt_bytes(const fhs_plaintext* pt) { return 8ull * pt->l * pt->ctx->N; }
 // The dense limbs of a plaintext.  A compact-only one (a periodic diagonal batch, encode_rows_dev) gets them on first
@@ -810,6 +832,8 @@ static fhs_status drop_pending(fhs_context* c, fhs_status st) {
     c->pending_l = -1;
     return st;
 }
+// the per-kernel event timer the launchers bracket with, when one is armed (fhs_kernel_timer)
+static const fhs::KTimer* ktimer(const fhs_context* c) { return c->timer_mask ? &c->ktimer : nullptr; }
 static fhs_status flush(fhs_context* c) {
     if (c->pending.empty()) return FHS_OK;
     const int R = (int)c->pending.size(), l = c->pending_l;
@@ -844,7 +868,7 @@ static fhs_status flush(fhs_context* c) {
         if (e != hipSuccess) return drop_pending(c, hip_fail(e, "seal corrections"));
     }
     e = fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), U, l, ws,
-                              wsb, c->items_dev, c->stager, c->st, c->timer_mask ? &c->ktimer : nullptr, sh);
+                              wsb, c->items_dev, c->stager, c->st, ktimer(c), sh);
     ht.mark("flush: launch keyswitch");
     if (e != hipSuccess) return drop_pending(c, hip_fail(e, "key-switch launch"));
     return drop_pending(c, FHS_OK);
@@ -2391,6 +2415,20 @@ extern "C" fhs_status fhs_encrypt_symmetric_batch(fhs_context* c, fhs_secret_key
     }
     return bo.keep(FHS_OK);
 }
+// The head of both fhs_encode_encrypt_*_batch entries: `count` vectors of n values staged into dvals and encoded to
+// their rounded message coefficients in coef (count x N doubles, launch_encode_coef).  Both blocks are the caller's.
+static fhs_status encode_coef_batch(fhs_context* c, const double* values, size_t count, size_t n, bool is_real,
+                                    double scale, DevTmp& dvals, DevTmp& coef) {
+    const size_t stride = is_real ? n : 2 * n;
+    HIPCHK(dvals.alloc(8 * count * stride), "encode_encrypt");
+    HIPCHK(coef.alloc(8 * count * c->N), "encode_encrypt");
+    if (stride) HIPCHK(stage_h2d(c, dvals.p, values, 8 * count * stride), "encode_encrypt");
+    DevTmp tl(c);   // periodic rows: the sparse encoding, as encode_*_batch gives them
+    HIPCHK(enc_periods(c, dvals.as<const double>(), count, n, stride, is_real, tl), "encode_encrypt");
+    HIPCHK(fhs::launch_encode_coef(c->T, dvals.as<const double>(), (int)count, n, stride, is_real, scale,
+                                   coef.as<double>(), c->st, tl.as<const unsigned char>()), "encode_encrypt");
+    return FHS_OK;
+}
 // Extension (the client's encrypt_replicated of a stage's inputs, bg:53-58 / 124-127, in one pass):
 // encode `count` vectors of n values (real, or interleaved re/im) at `scale` and chain index ci and encrypt
 // them with sk -- limb for limb fhs_encode[_real]_batch followed by fhs_encrypt_symmetric_batch, without
@@ -2404,20 +2442,11 @@ extern "C" fhs_status fhs_encode_encrypt_symmetric_batch(fhs_context* c, fhs_sec
     if (st != FHS_OK) return st;
     if (count == 0) return FHS_OK;
     if (count > (size_t)kMaxBatch) return fail(FHS_ERR_INVALID, "encode_encrypt: at most 4096 vectors per call");
-    const size_t stride = is_real ? n : 2 * n, N = c->N;
-    const int l = c->L0 + 1 - ci;
     DevTmp dvals(c), coef(c);
-    HIPCHK(dvals.alloc(8 * count * stride), "encode_encrypt");
-    HIPCHK(coef.alloc(8 * count * N), "encode_encrypt");
-    if (stride) HIPCHK(stage_h2d(c, dvals.p, values, 8 * count * stride), "encode_encrypt");
-    {
-        DevTmp tl(c);   // periodic rows: the sparse encoding, as encode_*_batch gives them
-        HIPCHK(enc_periods(c, dvals.as<const double>(), count, n, stride, is_real != 0, tl), "encode_encrypt");
-        HIPCHK(fhs::launch_encode_coef(c->T, dvals.as<const double>(), (int)count, n, stride, is_real != 0, scale,
-                                       coef.as<double>(), c->st, tl.as<const unsigned char>()), "encode_encrypt");
-    }
+    st = encode_coef_batch(c, values, count, n, is_real != 0, scale, dvals, coef);
+    if (st != FHS_OK) return st;
     std::vector<double> scales(count, scale);
-    return encrypt_sym_core(c, sk, (int)count, l, ci, scales.data(), nullptr, coef.as<const double>(), outs);
+    return encrypt_sym_core(c, sk, (int)count, c->L0 + 1 - ci, ci, scales.data(), nullptr, coef.as<const double>(), outs);
 }
 // `count` public-key encryptions at l limbs with the counters ctr0 .. ctr0 + count - 1, which the caller has already
 // taken from the key (a failure below does not give them back: a mask stream is never used twice): of the
@@ -2430,11 +2459,10 @@ static constexpr size_t kPkScratchBytes = (size_t)1 << 30;
 static fhs_status encrypt_pk_core(fhs_context* c, fhs_public_key* pk, uint64_t ctr0, int count, int l, int ci,
                                   const double* scales, const fhs_plaintext* const* pts, const double* coef,
                                   fhs_ciphertext** outs) {
-    std::vector<fhs_ciphertext*> cts(count, nullptr);
-    BatchOutT<fhs_ciphertext> bo(cts.data(), count);
-    fhs_status s = new_cts(c, count, 2, ci, scales[0], cts);
+    CtBlock blk(c);
+    fhs_status s = blk.make(count, 2, ci, scales[0]);
     if (s != FHS_OK) return s;
-    for (int i = 0; i < count; ++i) cts[i]->scale = scales[i];
+    for (int i = 0; i < count; ++i) blk[i]->scale = scales[i];
     const size_t S = (size_t)l * c->N;
     const int run = (int)std::min<size_t>(count, std::max<size_t>(1, kPkScratchBytes / (24 * S)));
     const size_t ub_bytes = 24 * S * run, small_bytes = (3 * (size_t)c->N * run + 7) & ~(size_t)7;
@@ -2449,18 +2477,17 @@ static fhs_status encrypt_pk_core(fhs_context* c, fhs_public_key* pk, uint64_t c
         HIPCHK(stage_h2d(c, small + small_bytes, ptrs.data(), 8 * ptrs.size()), "encrypt");
         dptrs = reinterpret_cast<const fhs::u64* const*>(small + small_bytes);
     }
-    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    const fhs::KTimer* tm = ktimer(c);
     for (int i0 = 0; i0 < count; i0 += run) {
         const int n = std::min(run, count - i0);
         HIPCHK(fhs::launch_encrypt_pk_batch(c->T, pk->rng, stream_id(ST_ENC_ASYM, ctr0 + (uint64_t)i0, 0),
-                                            stream_id(0, 1, 0), cts[0]->d + (size_t)i0 * 2 * S, pk->pk,
+                                            stream_id(0, 1, 0), blk.base() + (size_t)i0 * 2 * S, pk->pk,
                                             pk->pk + (size_t)c->L0 * c->N, dptrs ? dptrs + i0 : nullptr,
                                             ptrs.size() == 1 ? ptrs[0] : nullptr,
                                             coef ? coef + (size_t)i0 * c->N : nullptr, n, l,
                                             reinterpret_cast<signed char*>(small), tmp.p, c->st, tm), "encrypt");
     }
-    for (int i = 0; i < count; ++i) outs[i] = cts[i];
-    return bo.keep(FHS_OK);
+    return blk.commit(outs);
 }
 extern "C" fhs_status fhs_encrypt_asymmetric(fhs_context* c, fhs_public_key* pk, const fhs_plaintext* pt,
                                              fhs_ciphertext** out) {
@@ -2511,20 +2538,11 @@ extern "C" fhs_status fhs_encode_encrypt_asymmetric_batch(fhs_context* c, fhs_pu
     if (count > (size_t)kMaxBatch) return fail(FHS_ERR_INVALID, "encode_encrypt: at most 4096 vectors per call");
     const uint64_t ctr0 = pk->ctr;
     pk->ctr += (uint64_t)count;
-    const size_t stride = is_real ? n : 2 * n, N = c->N;
-    const int l = c->L0 + 1 - ci;
     DevTmp dvals(c), coef(c);
-    HIPCHK(dvals.alloc(8 * count * stride), "encode_encrypt");
-    HIPCHK(coef.alloc(8 * count * N), "encode_encrypt");
-    if (stride) HIPCHK(stage_h2d(c, dvals.p, values, 8 * count * stride), "encode_encrypt");
-    {
-        DevTmp tl(c);   // periodic rows: the sparse encoding, as encode_*_batch gives them
-        HIPCHK(enc_periods(c, dvals.as<const double>(), count, n, stride, is_real != 0, tl), "encode_encrypt");
-        HIPCHK(fhs::launch_encode_coef(c->T, dvals.as<const double>(), (int)count, n, stride, is_real != 0, scale,
-                                       coef.as<double>(), c->st, tl.as<const unsigned char>()), "encode_encrypt");
-    }
+    st = encode_coef_batch(c, values, count, n, is_real != 0, scale, dvals, coef);
+    if (st != FHS_OK) return st;
     std::vector<double> scales(count, scale);
-    return encrypt_pk_core(c, pk, ctr0, (int)count, l, ci, scales.data(), nullptr, coef.as<const double>(), outs);
+    return encrypt_pk_core(c, pk, ctr0, (int)count, c->L0 + 1 - ci, ci, scales.data(), nullptr, coef.as<const double>(), outs);
 }
 extern "C" fhs_status fhs_decrypt(fhs_context* c, fhs_secret_key* sk, const fhs_ciphertext* ct, fhs_plaintext** out) {
     ENTER(c);
@@ -2540,6 +2558,38 @@ extern "C" fhs_status fhs_decrypt(fhs_context* c, fhs_secret_key* sk, const fhs_
 static fhs_status same_level(const fhs_ciphertext* a, const fhs_ciphertext* b) {
     if (a->ci != b->ci) return fail(FHS_ERR_LEVEL, "operands are at different chain indices");
     return FHS_OK;
+}
+// What the batched entries read off their ciphertext handles: the fields the pure validators of fhs_tables.h judge,
+// and the limbs.  append() adds those of in[0..n) after the null and lost checks, in order.
+struct CtFields {
+    std::vector<int> ncomp, ci;
+    std::vector<double> scale;
+    std::vector<const uint64_t*> d;
+    fhs_status append(const fhs_ciphertext* const* in, size_t n) {
+        for (size_t k = 0; k < n; ++k) {
+            if (!in[k]) return fail(FHS_ERR_INVALID, "null argument");
+            LIVE(in[k]);
+            ncomp.push_back(in[k]->ncomp);
+            ci.push_back(in[k]->ci);
+            scale.push_back(in[k]->scale);
+            d.push_back(in[k]->d);
+        }
+        return FHS_OK;
+    }
+};
+// a validator's rejection (fhs_tables.h ArgErr) as the entry's status
+static fhs_status fail_arg(ArgErr cls, const char* msg) {
+    return fail(cls == ARG_LEVEL ? FHS_ERR_LEVEL : cls == ARG_SCALE ? FHS_ERR_SCALE : FHS_ERR_INVALID, msg);
+}
+// The pointer lists of one launch over R items, staged in stream order into the context's pointer buffer: first[0..R),
+// then (second non-null) second[0..R).  *da and *db are the two lists on the device; *db is null without a second.
+static hipError_t stage_ptr_lists(fhs_context* c, const uint64_t* const* first, const uint64_t* const* second, int R,
+                                  const uint64_t* const** da, const uint64_t* const** db) {
+    std::vector<const uint64_t*> ptrs(first, first + R);
+    if (second) ptrs.insert(ptrs.end(), second, second + R);
+    *da = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
+    *db = second ? *da + R : nullptr;
+    return stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * ptrs.size());
 }
 
 static fhs_status binop(fhs_context* c, int op, const fhs_ciphertext* a, const fhs_ciphertext* b, fhs_ciphertext** out) {
@@ -2616,19 +2666,23 @@ extern "C" fhs_status fhs_multiply(fhs_context* c, const fhs_ciphertext* a, cons
     return FHS_OK;
 }
 
-static fhs_status run_keyswitch(fhs_context* c, std::vector<KsItem>& items, int l) {
-    const int R = (int)items.size();
-    std::vector<const uint64_t*> uniq;
+// Relinearisation of R three-component ciphertexts t3 [R][3][l][N] into dst [R][2][l][N] as ONE batched key switch
+// of component 2 (a = comp 2, add0 = comp 0, add1 = comp 1; R = U: every item has its own input).  ws: at least
+// wsb = keyswitch_workspace_bytes(R, R, l) bytes of key-switch workspace.
+static fhs_status relin_batch(fhs_context* c, const fhs_relin_key* rk, const uint64_t* t3, uint64_t* dst, int R, int l,
+                              uint64_t* ws, size_t wsb, const fhs::KTimer* tm) {
+    const size_t S = (size_t)l * c->N;
+    const uint64_t* akey = key_akey(c, rk->key);
+    std::vector<KsItem> items(R);
+    std::vector<const uint64_t*> uniq(R);
     for (int r = 0; r < R; ++r) {
-        items[r].src = (uint64_t)uniq.size();
-        uniq.push_back(items[r].a);
+        const uint64_t* t = t3 + (size_t)r * 3 * S;
+        uint64_t* o = dst + (size_t)r * 2 * S;
+        items[r] = KsItem{t + 2 * S, t, t + S, rk->key, o, o + S, 1, (uint64_t)r, akey};
+        uniq[r] = t + 2 * S;
     }
-    const size_t wsb = fhs::keyswitch_workspace_bytes(c->T, R, R, l);
-    uint64_t* ws = nullptr;
-    HIPCHK(scratch(c, fhs_context::SCR_KS, wsb, &ws), "key-switch workspace");
-    hipError_t e = fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), R,
-                                         l, ws, wsb, c->items_dev, c->stager, c->st, nullptr);
-    if (e != hipSuccess) return hip_fail(e, "key-switch");
+    HIPCHK(fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), R, l, ws,
+                                 wsb, c->items_dev, c->stager, c->st, tm), "key-switch");
     return FHS_OK;
 }
 
@@ -2639,9 +2693,10 @@ extern "C" fhs_status fhs_relinearize(fhs_context* c, const fhs_ciphertext* a, c
     LIVE(a);
     if (a->ncomp != 3) return fail(FHS_ERR_INVALID, "relinearize expects a 3-component ciphertext");
     NEW_CT(r, 2, a->ci, a->scale);
-    const size_t S = (size_t)a->l * c->N;
-    std::vector<KsItem> it{KsItem{a->d + 2 * S, a->d, a->d + S, rk->key, r->d, r->d + S, 1, 0, key_akey(c, rk->key)}};
-    fhs_status s = run_keyswitch(c, it, a->l);
+    const size_t wsb = fhs::keyswitch_workspace_bytes(c->T, 1, 1, a->l);
+    uint64_t* ws = nullptr;
+    HIPCHK(scratch(c, fhs_context::SCR_KS, wsb, &ws), "key-switch workspace");
+    fhs_status s = relin_batch(c, rk, a->d, r->d, 1, a->l, ws, wsb, nullptr);
     if (s != FHS_OK) return s;
     *out = r.release();
     return FHS_OK;
@@ -2795,32 +2850,30 @@ extern "C" fhs_status fhs_inner_sum_many(fhs_context* c, const fhs_ciphertext* c
         akeys[k] = key_akey(c, it->second);
     }
     const size_t S = (size_t)l * c->N, per = 2 * S;
-    // chunks of equal size (within one) under both bounds
-    const size_t item_ws = fhs::keyswitch_workspace_bytes(c->T, 1, 1, l);
-    const int rmax = (int)std::max<size_t>(1, std::min<size_t>(fhs_context::kMaxItems, kInnerSumWsCap / item_ws));
-    const int nchunks = (n + rmax - 1) / rmax, rchunk = (n + nchunks - 1) / nchunks;
+    // chunks of equal size (within one, the larger ones first) under both bounds; the workspace is the first chunk's
+    const std::vector<std::pair<int, int>> chunks =
+        batch_chunks(n, fhs::keyswitch_workspace_bytes(c->T, 1, 1, l), fhs_context::kMaxItems, kInnerSumWsCap);
+    const int rchunk = chunks[0].second;
     // every allocation before the first launch; the outputs are the caller's only on success
     uint64_t* ws = nullptr;
     const size_t wsb = K ? fhs::keyswitch_workspace_bytes(c->T, rchunk, rchunk, l) : 0;
     if (K) HIPCHK(scratch(c, fhs_context::SCR_KS, wsb, &ws), "key-switch workspace");
     DevTmp pong(c);
     if (K >= 2) HIPCHK(pong.alloc(8 * (size_t)n * per), "inner_sum_many");
-    std::vector<fhs_ciphertext*> held((size_t)n), cts;
-    BatchOutT<fhs_ciphertext> bo(held.data(), (size_t)n);   // out_array stays untouched unless the call succeeds
-    fhs_status s = new_cts(c, n, 2, ci, in[0]->scale, cts);
+    CtBlock blk(c);
+    fhs_status s = blk.make(n, 2, ci, in[0]->scale);
     if (s != FHS_OK) return s;
-    std::copy(cts.begin(), cts.end(), held.begin());
-    for (int i = 0; i < n; ++i) cts[i]->scale = in[i]->scale;
-    uint64_t* const res = cts[0]->d;   // [n][2][l][N]: one block (new_cts), or the single ciphertext
+    for (int i = 0; i < n; ++i) blk[i]->scale = in[i]->scale;
+    uint64_t* const res = blk.base();   // [n][2][l][N]
     if (K == 0) {
         for (int i = 0; i < n; ++i)
             HIPCHK(hipMemcpyAsync(res + (size_t)i * per, in[i]->d, 8 * per, hipMemcpyDeviceToDevice, c->st), "inner_sum_many");
     }
-    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    const fhs::KTimer* tm = ktimer(c);
     std::vector<KsItem> items;
     std::vector<const uint64_t*> uniq;
-    for (int i0 = 0; K && i0 < n; i0 += rchunk) {
-        const int R = std::min(rchunk, n - i0);
+    for (const auto& ch : chunks) {
+        const int i0 = ch.first, R = ch.second;
         items.assign(R, KsItem{});
         uniq.resize(R);
         for (int k = 0; k < K; ++k) {
@@ -2837,8 +2890,7 @@ extern "C" fhs_status fhs_inner_sum_many(fhs_context* c, const fhs_ciphertext* c
                                          ws, wsb, c->items_dev, c->stager, c->st, tm), "key-switch");
         }
     }
-    std::copy(cts.begin(), cts.end(), out_array);
-    return bo.keep(FHS_OK);
+    return blk.commit(out_array);
 }
 
 // ============================================================================ fused BSGS
@@ -2881,7 +2933,7 @@ static fhs_status bsgs_core(fhs_context* c, const fhs_ciphertext* const* baby, i
     const uint64_t* const* dpts = dbaby + G;
     uint64_t* inner = nullptr;
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_INNER, 8ull * Beff * 2 * S, &inner), "bsgs inner products");
-    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    const fhs::KTimer* tm = ktimer(c);
     const size_t wsb = std::max<size_t>(8, fhs::bsgs_workspace_bytes(c->T, Beff - 1, l));
     uint64_t* ws = nullptr;
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_WS, wsb, &ws), "bsgs workspace");
@@ -3032,7 +3084,7 @@ extern "C" fhs_status fhs_dot_product_many(fhs_context* c, const fhs_ciphertext*
     if (rescale && l < 2) return fail(FHS_ERR_LEVEL, "rescale_to_next: no level left (end of modulus switching chain)");
     const size_t S = (size_t)l * c->N;
     const double sc = q[0]->scale * db[0]->scale;
-    // every allocation before the first launch; the outputs are the caller's only on success (BatchOutT)
+    // every allocation before the first launch; the outputs are the caller's only on success (CtBlock)
     uint64_t *t3 = nullptr, *relin = nullptr, *ws = nullptr, *scr = nullptr;
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_INNER, 8ull * C * 3 * S, &t3), "dot_product_many");
     if (rk && rescale) HIPCHK(scratch(c, fhs_context::SCR_BSGS_SUM, 8ull * C * 2 * S, &relin), "dot_product_many");
@@ -3041,36 +3093,26 @@ extern "C" fhs_status fhs_dot_product_many(fhs_context* c, const fhs_ciphertext*
     if (rk) HIPCHK(scratch(c, fhs_context::SCR_KS, wsb, &ws), "key-switch workspace");
     const int ocomp = rk ? 2 : 3;
     if (rescale) HIPCHK(scratch(c, fhs_context::SCR_RESCALE, 8ull * ocomp * C * c->N, &scr), "rescale");
-    BatchOutT<fhs_ciphertext> bo(outs, (size_t)C);
-    std::vector<fhs_ciphertext*> cts;
-    fhs_status s = new_cts(c, C, ocomp, rescale ? ci + 1 : ci, rescale ? sc / (double)c->q[l - 1] : sc, cts);
+    CtBlock blk(c);
+    fhs_status s = blk.make(C, ocomp, rescale ? ci + 1 : ci, rescale ? sc / (double)c->q[l - 1] : sc);
     if (s != FHS_OK) return s;
-    std::copy(cts.begin(), cts.end(), outs);
-    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    uint64_t* const res = blk.base();   // [C][ocomp][l or l - 1][N]
+    const fhs::KTimer* tm = ktimer(c);
     HIPCHK(stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * (nq + nd)), "dot_product_many");
     const uint64_t* const* dq = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
     // the tensor sums land where the last stage reads them: the outputs' block itself when nothing follows
-    uint64_t* tdst = (!rk && !rescale) ? outs[0]->d : t3;
+    uint64_t* tdst = (!rk && !rescale) ? res : t3;
     HIPCHK(fhs::launch_dot_tensor(c->T, dq, dq + J, J, C, l, tdst, c->st, tm), "dot_product_many");
     if (rk) {
-        uint64_t* kdst = rescale ? relin : outs[0]->d;   // [C][2][l][N]
-        const uint64_t* akey = key_akey(c, rk->key);
+        uint64_t* kdst = rescale ? relin : res;   // [C][2][l][N]
         for (int c0 = 0; c0 < C; c0 += kDotKsBatch) {
-            const int R = std::min(kDotKsBatch, C - c0);
-            std::vector<KsItem> items(R);
-            std::vector<const uint64_t*> uniq(R);
-            for (int r = 0; r < R; ++r) {
-                const uint64_t* t = t3 + (size_t)(c0 + r) * 3 * S;
-                uint64_t* o = kdst + (size_t)(c0 + r) * 2 * S;
-                items[r] = KsItem{t + 2 * S, t, t + S, rk->key, o, o + S, 1, (uint64_t)r, akey};
-                uniq[r] = t + 2 * S;
-            }
-            HIPCHK(fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), R,
-                                         l, ws, wsb, c->items_dev, c->stager, c->st, tm), "key-switch");
+            s = relin_batch(c, rk, t3 + (size_t)c0 * 3 * S, kdst + (size_t)c0 * 2 * S, std::min(kDotKsBatch, C - c0), l, ws,
+                            wsb, tm);
+            if (s != FHS_OK) return s;
         }
     }
-    if (rescale) HIPCHK(fhs::launch_rescale(c->T, rk ? relin : t3, outs[0]->d, scr, ocomp * C, l, c->st, tm), "rescale");
-    return bo.keep(FHS_OK);
+    if (rescale) HIPCHK(fhs::launch_rescale(c->T, rk ? relin : t3, res, scr, ocomp * C, l, c->st, tm), "rescale");
+    return blk.commit(outs);
 }
 
 // ============================================================================ batched multiply, relinearize, rescale
@@ -3089,18 +3131,16 @@ extern "C" fhs_status fhs_multiply_relin_many(fhs_context* c, const fhs_cipherte
                                               fhs_ciphertext** out_array) {
     ENTER(c);
     const bool null_arg = !a || !out_array;
-    const size_t cnt = (null_arg || n < 1) ? 0 : (size_t)n * (b ? 2 : 1);
-    std::vector<int> ncomp(cnt), cis(cnt);
-    for (size_t k = 0; k < cnt; ++k) {
-        const fhs_ciphertext* x = k < (size_t)n ? a[k] : b[k - n];
-        if (!x) return fail(FHS_ERR_INVALID, "null argument");
-        LIVE(x);
-        ncomp[k] = x->ncomp;
-        cis[k] = x->ci;
+    CtFields h;   // a's then b's
+    fhs_status s = FHS_OK;
+    if (!null_arg && n >= 1) {
+        s = h.append(a, (size_t)n);
+        if (s == FHS_OK && b) s = h.append(b, (size_t)n);
     }
-    bool level = false;
-    if (const char* bad = multiply_many_error(null_arg, n, ncomp.data(), cis.data(), cnt, c->L0, rescale, &level))
-        return fail(level ? FHS_ERR_LEVEL : FHS_ERR_INVALID, bad);
+    if (s != FHS_OK) return s;
+    ArgErr cls;
+    if (const char* bad = multiply_many_error(null_arg, n, h.ncomp.data(), h.ci.data(), h.ci.size(), c->L0, rescale, &cls))
+        return fail_arg(cls, bad);
     const int ci = a[0]->ci, l = a[0]->l, ocomp = rk ? 2 : 3;
     const size_t S = (size_t)l * c->N;
     // chunks of equal size (within one) under both bounds; the scratch is the largest (first) chunk's
@@ -3115,21 +3155,16 @@ extern "C" fhs_status fhs_multiply_relin_many(fhs_context* c, const fhs_cipherte
     const size_t wsb = rk ? fhs::keyswitch_workspace_bytes(c->T, Rmax, Rmax, l) : 0;
     if (rk) HIPCHK(scratch(c, fhs_context::SCR_KS, wsb, &ws), "key-switch workspace");
     if (rescale) HIPCHK(scratch(c, fhs_context::SCR_RESCALE, 8ull * ocomp * Rmax * c->N, &scr), "rescale");
-    std::vector<fhs_ciphertext*> held((size_t)n), cts;
-    BatchOutT<fhs_ciphertext> bo(held.data(), (size_t)n);
-    fhs_status s = new_cts(c, n, ocomp, rescale ? ci + 1 : ci, 1.0, cts);
+    CtBlock blk(c);
+    s = blk.make(n, ocomp, rescale ? ci + 1 : ci, 1.0);
     if (s != FHS_OK) return s;
-    std::copy(cts.begin(), cts.end(), held.begin());
     for (int i = 0; i < n; ++i) {
         const double sc = a[i]->scale * (b ? b[i] : a[i])->scale;   // fhs_multiply's, then fhs_rescale_to_next's
-        cts[i]->scale = rescale ? sc / (double)c->q[l - 1] : sc;
+        blk[i]->scale = rescale ? sc / (double)c->q[l - 1] : sc;
     }
-    uint64_t* const res = cts[0]->d;   // [n][ocomp][l or l - 1][N]: one block (new_cts), or the single ciphertext
-    const size_t per_out = (size_t)ocomp * (rescale ? l - 1 : l) * c->N;
-    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
-    const uint64_t* akey = rk ? key_akey(c, rk->key) : nullptr;
-    std::vector<const uint64_t*> ptrs, uniq;
-    std::vector<KsItem> items;
+    uint64_t* const res = blk.base();   // [n][ocomp][l or l - 1][N]
+    const size_t per_out = blk.words_per_ct();
+    const fhs::KTimer* tm = ktimer(c);
     for (const auto& ch : chunks) {
         const int i0 = ch.first, R = ch.second;
         uint64_t* const slice = res + (size_t)i0 * per_out;
@@ -3139,33 +3174,18 @@ extern "C" fhs_status fhs_multiply_relin_many(fhs_context* c, const fhs_cipherte
             HIPCHK(fhs::launch_tensor(c->T, nullptr, nullptr, a[i0]->d, (b ? b[i0] : a[i0])->d, 1, tdst, l, c->st),
                    "multiply_relin_many");
         } else {
-            // the chunk's pointer lists, a's then b's (squares: a's alone, read as both), staged in stream order
-            ptrs.resize((size_t)R * (b ? 2 : 1));
-            for (int r = 0; r < R; ++r) {
-                ptrs[r] = a[i0 + r]->d;
-                if (b) ptrs[R + r] = b[i0 + r]->d;
-            }
-            HIPCHK(stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * ptrs.size()), "multiply_relin_many");
-            const uint64_t* const* da = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
-            HIPCHK(fhs::launch_tensor(c->T, da, b ? da + R : da, nullptr, nullptr, R, tdst, l, c->st), "multiply_relin_many");
+            // the chunk's pointer lists, a's then b's (squares: a's alone, read as both)
+            const uint64_t *const *da = nullptr, *const *db = nullptr;
+            HIPCHK(stage_ptr_lists(c, h.d.data() + i0, b ? h.d.data() + n + i0 : nullptr, R, &da, &db), "multiply_relin_many");
+            HIPCHK(fhs::launch_tensor(c->T, da, b ? db : da, nullptr, nullptr, R, tdst, l, c->st), "multiply_relin_many");
         }
         if (rk) {
-            uint64_t* const kdst = rescale ? relin : slice;   // [R][2][l][N]
-            items.resize(R);
-            uniq.resize(R);
-            for (int r = 0; r < R; ++r) {
-                const uint64_t* t = t3 + (size_t)r * 3 * S;
-                uint64_t* o = kdst + (size_t)r * 2 * S;
-                items[r] = KsItem{t + 2 * S, t, t + S, rk->key, o, o + S, 1, (uint64_t)r, akey};
-                uniq[r] = t + 2 * S;
-            }
-            HIPCHK(fhs::launch_keyswitch(c->T, items.data(), R, reinterpret_cast<const fhs::u64* const*>(uniq.data()), R, l,
-                                         ws, wsb, c->items_dev, c->stager, c->st, tm), "key-switch");
+            s = relin_batch(c, rk, t3, rescale ? relin : slice, R, l, ws, wsb, tm);
+            if (s != FHS_OK) return s;
         }
         if (rescale) HIPCHK(fhs::launch_rescale(c->T, rk ? relin : t3, slice, scr, ocomp * R, l, c->st, tm), "rescale");
     }
-    std::copy(cts.begin(), cts.end(), out_array);
-    return bo.keep(FHS_OK);
+    return blk.commit(out_array);
 }
 
 // ============================================================================ batched CT x PT multiply and rescale
@@ -3179,17 +3199,17 @@ extern "C" fhs_status fhs_multiply_plain_rescale_many(fhs_context* c, const fhs_
     ENTER(c);
     const bool null_arg = !a || !out_array;
     const int cnt = (null_arg || n < 1) ? 0 : n;
-    std::vector<int> ncomp(cnt), cis(cnt), pcis(p ? cnt : 0);
-    for (int k = 0; k < cnt; ++k) {
-        if (!a[k] || (p && !p[k])) return fail(FHS_ERR_INVALID, "null argument");
-        LIVE(a[k]);
-        ncomp[k] = a[k]->ncomp;
-        cis[k] = a[k]->ci;
+    CtFields h;
+    std::vector<int> pcis(p ? cnt : 0);
+    for (int k = 0; k < cnt; ++k) {   // pair by pair: a null plaintext is reported before a lost ciphertext after it
+        if (p && !p[k]) return fail(FHS_ERR_INVALID, "null argument");
+        const fhs_status s = h.append(a + k, 1);
+        if (s != FHS_OK) return s;
         if (p) pcis[k] = p[k]->ci;
     }
-    bool level = false;
-    if (const char* bad = mulp_rescale_many_error(null_arg, n, ncomp.data(), cis.data(), p ? pcis.data() : nullptr, c->L0, &level))
-        return fail(level ? FHS_ERR_LEVEL : FHS_ERR_INVALID, bad);
+    ArgErr cls;
+    if (const char* bad = mulp_rescale_many_error(null_arg, n, h.ncomp.data(), h.ci.data(), p ? pcis.data() : nullptr, c->L0, &cls))
+        return fail_arg(cls, bad);
     const int ci = a[0]->ci, l = a[0]->l;
     const size_t N = c->N;
     const std::vector<std::pair<int, int>> chunks = mulp_rescale_chunks(n, N);
@@ -3197,11 +3217,9 @@ extern "C" fhs_status fhs_multiply_plain_rescale_many(fhs_context* c, const fhs_
     // every allocation before the first launch of the call's own kernels; out_array is written only on success
     uint64_t* scr = nullptr;
     HIPCHK(scratch(c, fhs_context::SCR_RESCALE, mulp_rescale_item_bytes(N) * Rmax, &scr), "rescale");
-    std::vector<fhs_ciphertext*> held((size_t)n), cts;
-    BatchOutT<fhs_ciphertext> bo(held.data(), (size_t)n);
-    fhs_status s = new_cts(c, n, 2, ci + 1, 1.0, cts);
+    CtBlock blk(c);
+    fhs_status s = blk.make(n, 2, ci + 1, 1.0);
     if (s != FHS_OK) return s;
-    std::copy(cts.begin(), cts.end(), held.begin());
     std::vector<const uint64_t*> pd(p ? n : 0);
     for (int i = 0; i < n; ++i) {
         double sc = a[i]->scale;                       // fhs_multiply_plain's, then fhs_rescale_to_next's
@@ -3209,27 +3227,20 @@ extern "C" fhs_status fhs_multiply_plain_rescale_many(fhs_context* c, const fhs_
             sc = a[i]->scale * p[i]->scale;
             HIPCHK(pt_dense(c, p[i], &pd[i]), "multiply_plain_rescale_many");   // a compact-only plaintext's dense limbs
         }
-        cts[i]->scale = sc / (double)c->q[l - 1];
+        blk[i]->scale = sc / (double)c->q[l - 1];
     }
-    uint64_t* const res = cts[0]->d;   // [n][2][l - 1][N]: one block (new_cts), or the single ciphertext
-    const size_t per_out = 2 * (size_t)(l - 1) * N;
-    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
-    std::vector<const uint64_t*> ptrs;
+    uint64_t* const res = blk.base();   // [n][2][l - 1][N]
+    const size_t per_out = blk.words_per_ct();
+    const fhs::KTimer* tm = ktimer(c);
     for (const auto& ch : chunks) {
         const int i0 = ch.first, R = ch.second;
-        // the chunk's pointer lists, the ciphertexts' then the plaintexts', staged in stream order
-        ptrs.resize((size_t)R * (p ? 2 : 1));
-        for (int r = 0; r < R; ++r) {
-            ptrs[r] = a[i0 + r]->d;
-            if (p) ptrs[R + r] = pd[i0 + r];
-        }
-        HIPCHK(stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * ptrs.size()), "multiply_plain_rescale_many");
-        const uint64_t* const* da = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
-        HIPCHK(fhs::launch_rescale_many(c->T, da, p ? da + R : nullptr, R, l, res + (size_t)i0 * per_out, scr, c->st, tm),
+        // the chunk's pointer lists, the ciphertexts' then the plaintexts'
+        const uint64_t *const *da = nullptr, *const *dp = nullptr;
+        HIPCHK(stage_ptr_lists(c, h.d.data() + i0, p ? pd.data() + i0 : nullptr, R, &da, &dp), "multiply_plain_rescale_many");
+        HIPCHK(fhs::launch_rescale_many(c->T, da, dp, R, l, res + (size_t)i0 * per_out, scr, c->st, tm),
                "multiply_plain_rescale_many");
     }
-    std::copy(cts.begin(), cts.end(), out_array);
-    return bo.keep(FHS_OK);
+    return blk.commit(out_array);
 }
 
 // ============================================================================ plaintext-weighted sums of ciphertexts
@@ -3247,20 +3258,12 @@ extern "C" fhs_status fhs_weighted_sums(fhs_context* c, const fhs_ciphertext* co
     ENTER(c);
     const bool null_arg = !in || !W || !out_array;
     const int cnt = (null_arg || F < 1 || F > kWsumMaxF) ? 0 : F;
-    std::vector<int> ncomp(cnt), cis(cnt);
-    std::vector<double> scs(cnt);
-    std::vector<const uint64_t*> ptrs(cnt);
-    for (int j = 0; j < cnt; ++j) {
-        if (!in[j]) return fail(FHS_ERR_INVALID, "null argument");
-        LIVE(in[j]);
-        ncomp[j] = in[j]->ncomp;
-        cis[j] = in[j]->ci;
-        scs[j] = in[j]->scale;
-        ptrs[j] = in[j]->d;
-    }
-    WsumErr cls = WSUM_INVALID;
-    if (const char* bad = weighted_sums_error(null_arg, F, E, ldw, scale, ncomp.data(), cis.data(), scs.data(), c->L0, &cls))
-        return fail(cls == WSUM_LEVEL ? FHS_ERR_LEVEL : cls == WSUM_SCALE ? FHS_ERR_SCALE : FHS_ERR_INVALID, bad);
+    CtFields h;
+    fhs_status s = h.append(in, (size_t)cnt);
+    if (s != FHS_OK) return s;
+    ArgErr cls;
+    if (const char* bad = weighted_sums_error(null_arg, F, E, ldw, scale, h.ncomp.data(), h.ci.data(), h.scale.data(), c->L0, &cls))
+        return fail_arg(cls, bad);
     const int ci = in[0]->ci, l = in[0]->l, lm = l - 1;
     if (c->N % 2) return fail(FHS_ERR_INVALID, "weighted_sums: poly_modulus_degree must be even");
     WsumTables Wt;
@@ -3276,27 +3279,24 @@ extern "C" fhs_status fhs_weighted_sums(fhs_context* c, const fhs_ciphertext* co
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_INNER, 16 * Rmax * lm * N, &tcorr), "weighted_sums");
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_WS, 8 * (Wt.wl.size() + Wt.wt.size()), &wdev), "weighted_sums");
     HIPCHK(scratch(c, fhs_context::SCR_ENC_PTRS, 16 * Rmax, &tptrs), "weighted_sums");
-    std::vector<fhs_ciphertext*> held((size_t)E), cts;
-    BatchOutT<fhs_ciphertext> bo(held.data(), (size_t)E);
-    fhs_status s = new_cts(c, E, 2, ci + 1, in[0]->scale * scale / (double)c->q[l - 1], cts);
+    CtBlock blk(c);
+    s = blk.make(E, 2, ci + 1, in[0]->scale * scale / (double)c->q[l - 1]);
     if (s != FHS_OK) return s;
-    std::copy(cts.begin(), cts.end(), held.begin());
-    uint64_t* const res = cts[0]->d;   // [E][2][l - 1][N]: one block (new_cts), or the single ciphertext
+    uint64_t* const res = blk.base();   // [E][2][l - 1][N]
     uint64_t* const wt_dev = wdev + Wt.wl.size();
     std::vector<uint64_t*> tp(2 * Rmax);
     for (size_t v = 0; v < 2 * Rmax; ++v) tp[v] = tcorr + v * lm * N;
-    HIPCHK(stage_h2d(c, c->ptrs_dev, ptrs.data(), sizeof(void*) * ptrs.size()), "weighted_sums");
+    HIPCHK(stage_h2d(c, c->ptrs_dev, h.d.data(), sizeof(void*) * h.d.size()), "weighted_sums");
     HIPCHK(stage_h2d(c, tptrs, tp.data(), sizeof(void*) * tp.size()), "weighted_sums");
     HIPCHK(stage_h2d(c, wdev, Wt.wl.data(), 8 * Wt.wl.size()), "weighted_sums");
     HIPCHK(stage_h2d(c, wt_dev, Wt.wt.data(), 8 * Wt.wt.size()), "weighted_sums");
     const uint64_t* const* din = reinterpret_cast<const uint64_t* const*>(c->ptrs_dev);
-    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    const fhs::KTimer* tm = ktimer(c);
     HIPCHK(fhs::launch_last_limbs_intt(c->T, din, F, l, dco, c->st, tm), "weighted_sums");
     for (const auto& ch : chunks)
         HIPCHK(fhs::launch_wsum_chunk(c->T, din, dco, wdev, wt_dev, F, Wt.Epad, ch.first, ch.second, l, planes, tcorr,
                                       reinterpret_cast<fhs::u64* const*>(tptrs), res, c->st, tm), "weighted_sums");
-    std::copy(cts.begin(), cts.end(), out_array);
-    return bo.keep(FHS_OK);
+    return blk.commit(out_array);
 }
 
 // Test hooks: the per-coefficient routines of fhs_weighted_sums' two pointwise stages (fhs_modarith.h wsum_round_*,
@@ -3402,7 +3402,7 @@ static fhs_status giant_steps_core(fhs_context* c, Src src, int k, int ci, doubl
     const size_t wsb = std::max<size_t>(8, fhs::bsgs_workspace_bytes(c->T, B - 1, l));
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_WS, wsb, &ws), "bsgs_giant_steps");
     HIPCHK(scratch(c, fhs_context::SCR_BSGS_SUM, 16 * S, &sum), "bsgs_giant_steps");
-    const fhs::KTimer* tm = c->timer_mask ? &c->ktimer : nullptr;
+    const fhs::KTimer* tm = ktimer(c);
     HIPCHK(fhs::launch_bsgs(c->T, nullptr, nullptr, 1, B, B, l, keys.data(), akeys.data(), ge.data(), inner, sum, ws, wsb,
                             c->items_dev, c->stager, c->st, tm, 0, &c->side),
            "bsgs_giant_steps");

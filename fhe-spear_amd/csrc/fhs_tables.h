@@ -287,24 +287,26 @@ static const char* inner_sum_steps(int n, int dim, int stride, uint64_t N, std::
     return nullptr;
 }
 
+// The status class of the argument a batched entry's validator rejects (the host's fail_arg maps it to FHS_ERR_INVALID,
+// FHS_ERR_LEVEL or FHS_ERR_SCALE); an accepted call leaves ARG_INVALID.
+enum ArgErr { ARG_INVALID, ARG_LEVEL, ARG_SCALE };
 // The arguments of fhs_multiply_relin_many, from what the host layer reads off the handles: n pairs, `count`
 // operand entries (n for squares, 2 n for pairs: a's then b's) with their component counts and chain indices, the
-// context's L0 and the rescale flag.  The message of the first argument that is wrong, or null; *level is set when
-// that argument is a level error (FHS_ERR_LEVEL) rather than an invalid one.
+// context's L0 and the rescale flag.  The message of the first argument that is wrong, or null; *cls is its class.
 static const char* multiply_many_error(bool null_arg, int n, const int* ncomp, const int* ci, size_t count, int L0,
-                                       int rescale, bool* level) {
-    *level = false;
+                                       int rescale, ArgErr* cls) {
+    *cls = ARG_INVALID;
     if (null_arg) return "null argument";
     if (n < 1) return "multiply_relin_many: n >= 1";
     if (!ncomp || !ci || count < (size_t)n) return "null argument";
     for (size_t k = 0; k < count; ++k)
         if (ncomp[k] != 2) return "multiply expects 2-component ciphertexts";
-    *level = true;
+    *cls = ARG_LEVEL;
     for (size_t k = 1; k < count; ++k)
         if (ci[k] != ci[0]) return "multiply_relin_many: inputs must share one chain index";
     if (ci[0] < 1 || ci[0] > L0) return "chain index out of range";
     if (rescale && L0 + 1 - ci[0] < 2) return "rescale_to_next: no level left (end of modulus switching chain)";
-    *level = false;
+    *cls = ARG_INVALID;
     return nullptr;
 }
 // The item buffer of a key-switch launch (fhs_context::kMaxItems) and the scratch a chunk of fhs_multiply_relin_many
@@ -339,24 +341,23 @@ static std::vector<std::pair<int, int>> batch_chunks(int n, size_t item_bytes, i
 // ============================================================================ fhs_multiply_plain_rescale_many (host side)
 // The arguments of fhs_multiply_plain_rescale_many, from what the host layer reads off the handles: the n
 // ciphertexts' component counts and chain indices and (pci non-null: the call has plaintexts) the n plaintexts' chain
-// indices.  The message of the first argument that is wrong, or null; *level is set when that argument is a level
-// error (FHS_ERR_LEVEL) rather than an invalid one.
+// indices.  The message of the first argument that is wrong, or null; *cls is its class.
 static const char* mulp_rescale_many_error(bool null_arg, int n, const int* ncomp, const int* ci, const int* pci, int L0,
-                                           bool* level) {
-    *level = false;
+                                           ArgErr* cls) {
+    *cls = ARG_INVALID;
     if (null_arg) return "null argument";
     if (n < 1) return "multiply_plain_rescale_many: n >= 1";
     if (!ncomp || !ci) return "null argument";
     for (int k = 0; k < n; ++k)
         if (ncomp[k] != 2) return "multiply_plain_rescale_many expects 2-component ciphertexts";
-    *level = true;
+    *cls = ARG_LEVEL;
     for (int k = 1; k < n; ++k)
         if (ci[k] != ci[0]) return "multiply_plain_rescale_many: inputs must share one chain index";
     for (int k = 0; pci && k < n; ++k)
         if (pci[k] != ci[0]) return "ciphertext and plaintext are at different chain indices";
     if (ci[0] < 1 || ci[0] > L0) return "chain index out of range";
     if (L0 + 1 - ci[0] < 2) return "rescale_to_next: no level left (end of modulus switching chain)";
-    *level = false;
+    *cls = ARG_INVALID;
     return nullptr;
 }
 // The chunks of one call over n items at ring size N.  An item is one (ciphertext, plaintext) pair: two staged device
@@ -378,12 +379,11 @@ static std::vector<std::pair<int, int>> mulp_rescale_chunks(int n, size_t N, siz
 static bool scales_close(double a, double b) { return std::fabs(a - b) <= 1e-9 * std::max(std::fabs(a), std::fabs(b)); }
 constexpr int kWsumMaxF = 4096;               // inputs per call: the rounding sum stays below 2^72 (wsum_round_term)
 constexpr int kWsumMaxOutputs = kKsMaxItems;  // outputs per chunk
-enum WsumErr { WSUM_INVALID = 0, WSUM_LEVEL = 1, WSUM_SCALE = 2 };
 // The arguments of fhs_weighted_sums, from what the host layer reads off the F handles (component counts, chain
 // indices, scales).  The message of the first argument that is wrong, or null; *cls is its status class.
 static const char* weighted_sums_error(bool null_arg, int F, int E, int64_t ldw, double scale, const int* ncomp,
-                                       const int* ci, const double* scales, int L0, WsumErr* cls) {
-    *cls = WSUM_INVALID;
+                                       const int* ci, const double* scales, int L0, ArgErr* cls) {
+    *cls = ARG_INVALID;
     if (null_arg) return "null argument";
     if (F < 1 || F > kWsumMaxF) return "weighted_sums: 1 <= F <= 4096";
     if (E < 1) return "weighted_sums: E >= 1";
@@ -392,15 +392,15 @@ static const char* weighted_sums_error(bool null_arg, int F, int E, int64_t ldw,
     if (!ncomp || !ci || !scales) return "null argument";
     for (int j = 0; j < F; ++j)
         if (ncomp[j] != 2) return "weighted_sums expects 2-component ciphertexts";
-    *cls = WSUM_LEVEL;
+    *cls = ARG_LEVEL;
     for (int j = 1; j < F; ++j)
         if (ci[j] != ci[0]) return "weighted_sums: inputs must share one chain index";
     if (ci[0] < 1 || ci[0] > L0) return "chain index out of range";
     if (L0 + 1 - ci[0] < 2) return "rescale_to_next: no level left (end of modulus switching chain)";
-    *cls = WSUM_SCALE;
+    *cls = ARG_SCALE;
     for (int j = 1; j < F; ++j)
         if (!scales_close(scales[j], scales[0])) return "scale mismatch";
-    *cls = WSUM_INVALID;
+    *cls = ARG_INVALID;
     return nullptr;
 }
 // The weight tables of one call at l limbs (L = l - 1, the limb the rescale drops): the plaintext of (output i, input j)

@@ -528,6 +528,16 @@ def _pt(ctx, fn, *args, what=""):
     return plaintext(ctx, h)
 
 
+def _handles(objs, n=None):
+    """The handles of `objs` as a _vp array of n entries (default: one per object; a longer array ends in nulls)."""
+    return (_vp * (len(objs) if n is None else n))(*[o._h for o in objs])
+
+
+def _ct_list(ctx, outs, n):
+    """The first n handles of an output array as ciphertexts."""
+    return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+
+
 # ------------------------------------------------------------------ keys (pb:100-122)
 class public_key:
     def __init__(self, _ctx=None, _h=None):
@@ -548,10 +558,9 @@ class public_key:
         n = len(pts)
         if n == 0:
             return []
-        ins = (_vp * n)(*[p._h for p in pts])
         outs = (_vp * n)()
-        _check(_lib.fhs_encrypt_asymmetric_batch(ctx._h, self._h, ins, n, outs), "encrypt_asymmetric_batch")
-        return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+        _check(_lib.fhs_encrypt_asymmetric_batch(ctx._h, self._h, _handles(pts), n, outs), "encrypt_asymmetric_batch")
+        return _ct_list(ctx, outs, n)
 
     def encode_encrypt_batch(self, ctx, mat, scale, chain_index=1):
         """Extension: one ciphertext per row of `mat` (real rows: encode_double_vector_batch, complex rows:
@@ -570,7 +579,7 @@ class public_key:
             _check(_lib.fhs_encode_encrypt_asymmetric_batch(ctx._h, self._h, part.ctypes.data_as(_dblp), len(part), n,
                                                             0 if cplx else 1, float(scale), int(chain_index), outs),
                    "encode_encrypt_batch")
-            res += [ciphertext(ctx, _vp(outs[i])) for i in range(len(part))]
+            res += _ct_list(ctx, outs, len(part))
         return res
 
 
@@ -666,10 +675,9 @@ class secret_key:
         n = len(pts)
         if n == 0:
             return []
-        ins = (_vp * n)(*[p._h for p in pts])
         outs = (_vp * n)()
-        _check(_lib.fhs_encrypt_symmetric_batch(ctx._h, self._h, ins, n, outs), "encrypt_symmetric_batch")
-        return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+        _check(_lib.fhs_encrypt_symmetric_batch(ctx._h, self._h, _handles(pts), n, outs), "encrypt_symmetric_batch")
+        return _ct_list(ctx, outs, n)
 
     def encode_encrypt_batch(self, ctx, mat, scale, chain_index=1):
         """Extension: one ciphertext per row of `mat` (real rows: encode_double_vector_batch, complex rows:
@@ -686,7 +694,7 @@ class secret_key:
         _check(_lib.fhs_encode_encrypt_symmetric_batch(ctx._h, self._h, m.ctypes.data_as(_dblp), count, n,
                                                        0 if cplx else 1, float(scale), int(chain_index), outs),
                "encode_encrypt_batch")
-        return [ciphertext(ctx, _vp(outs[i])) for i in range(count)]
+        return _ct_list(ctx, outs, count)
 
     def decrypt_decode_batch(self, ctx, cts, nslots=None):
         """Extension: decrypt each ciphertext and decode its first `nslots` slots (default all) -- the
@@ -694,7 +702,7 @@ class secret_key:
         complex array [len(cts), nslots]."""
         n = ctx.N // 2 if nslots is None else int(nslots)
         out = np.empty((len(cts), n, 2), dtype=np.float64)
-        hs = (_vp * max(1, len(cts)))(*[c._h for c in cts])
+        hs = _handles(cts, max(1, len(cts)))
         _check(_lib.fhs_decrypt_decode_batch(ctx._h, self._h, hs, len(cts), n, out.ctypes.data_as(_dblp)),
                "decrypt_decode_batch")
         return out[..., 0] + 1j * out[..., 1]
@@ -813,7 +821,7 @@ class ckks_encoder:
         values decode_complex_vector gives."""
         n = ctx.N // 2 if nslots is None else int(nslots)
         out = np.empty((len(pts), n, 2), dtype=np.float64)
-        hs = (_vp * max(1, len(pts)))(*[p._h for p in pts])
+        hs = _handles(pts, max(1, len(pts)))
         _check(_lib.fhs_decode_batch(ctx._h, hs, len(pts), n, out.ctypes.data_as(_dblp)), "decode_batch")
         return out[..., 0] + 1j * out[..., 1]
 
@@ -894,11 +902,10 @@ def hoisting(ctx, a, gk, steps):
     """pb:205: all rotations of one ciphertext (batched in one key-switch launch)."""
     steps = [int(s) for s in steps]
     n = len(steps)
-    ins = (_vp * n)(*([a._h] * n))
     st = (C.c_int * n)(*steps)
     outs = (_vp * n)()
-    _check(_lib.fhs_rotate_many(ctx._h, ins, st, n, gk._h, outs), "hoisting")
-    return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+    _check(_lib.fhs_rotate_many(ctx._h, _handles([a] * n), st, n, gk._h, outs), "hoisting")
+    return _ct_list(ctx, outs, n)
 
 
 def inner_sum_many(ctx, cts, dim, gk, stride=1):
@@ -909,10 +916,9 @@ def inner_sum_many(ctx, cts, dim, gk, stride=1):
     may differ.  The results share one device block."""
     cts = list(cts)
     n = len(cts)
-    ins = (_vp * n)(*[c._h for c in cts])
     outs = (_vp * n)()
-    _check(_lib.fhs_inner_sum_many(ctx._h, ins, n, int(dim), int(stride), gk._h, outs), "inner_sum_many")
-    return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+    _check(_lib.fhs_inner_sum_many(ctx._h, _handles(cts), n, int(dim), int(stride), gk._h, outs), "inner_sum_many")
+    return _ct_list(ctx, outs, n)
 
 
 def inner_sum(ctx, ct, dim, gk, stride=1):
@@ -945,11 +951,10 @@ def multiply_plain_rescale_many(ctx, cts, pts):
     if pts is not None:
         if len(pts) != n:
             raise ValueError(f"multiply_plain_rescale_many: lists of different length ({n} and {len(pts)})")
-        pp = (_vp * max(n, 1))(*[p._h for p in pts])
-    aa = (_vp * max(n, 1))(*[c._h for c in cts])
+        pp = _handles(pts, max(n, 1))
     outs = (_vp * max(n, 1))()
-    _check(_lib.fhs_multiply_plain_rescale_many(ctx._h, aa, pp, n, outs), "multiply_plain_rescale_many")
-    return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+    _check(_lib.fhs_multiply_plain_rescale_many(ctx._h, _handles(cts, max(n, 1)), pp, n, outs), "multiply_plain_rescale_many")
+    return _ct_list(ctx, outs, n)
 
 
 def rescale_many(ctx, cts):
@@ -980,9 +985,8 @@ def ct_pt_dot_columns(ctx, ct, W, dim, scale, gk):
 def bsgs_multiply_accumulate(ctx, ct_baby, pts, G, B, D, gk):
     """bg:459 / bg:515 fused BSGS; limb-identical to the loop bg:464-485 (incl. final rescale)."""
     G, B, D = int(G), int(B), int(D)
-    bb = (_vp * G)(*[c._h for c in ct_baby[:G]])
-    pp = (_vp * D)(*[p._h for p in pts[:D]])
-    return _ct(ctx, _lib.fhs_bsgs_multiply_accumulate, bb, G, pp, D, B, gk._h, what="bsgs_multiply_accumulate")
+    return _ct(ctx, _lib.fhs_bsgs_multiply_accumulate, _handles(ct_baby[:G], G), G, _handles(pts[:D], D), D, B, gk._h,
+               what="bsgs_multiply_accumulate")
 
 
 def bsgs_inner_products(ctx, ct_baby, pts, G, B):
@@ -991,11 +995,9 @@ def bsgs_inner_products(ctx, ct_baby, pts, G, B):
     G, B = int(G), int(B)
     if len(pts) != G * B:
         raise ValueError(f"bsgs_inner_products: {len(pts)} plaintexts for G={G}, B={B}")
-    bb = (_vp * G)(*[c._h for c in ct_baby[:G]])
-    pp = (_vp * (G * B))(*[p._h for p in pts])
     hs = (_vp * B)()
-    _check(_lib.fhs_bsgs_inner_products(ctx._h, bb, G, pp, B, hs), "bsgs_inner_products")
-    return [ciphertext(ctx, _vp(hs[g])) for g in range(B)]
+    _check(_lib.fhs_bsgs_inner_products(ctx._h, _handles(ct_baby[:G], G), G, _handles(pts), B, hs), "bsgs_inner_products")
+    return _ct_list(ctx, hs, B)
 
 
 def bsgs_inner_products_to_device(ctx, ct_baby, pts, G, B, dst_ptr):
@@ -1004,9 +1006,8 @@ def bsgs_inner_products_to_device(ctx, ct_baby, pts, G, B, dst_ptr):
     G, B = int(G), int(B)
     if len(pts) != G * B:
         raise ValueError(f"bsgs_inner_products_to_device: {len(pts)} plaintexts for G={G}, B={B}")
-    bb = (_vp * G)(*[c._h for c in ct_baby[:G]])
-    pp = (_vp * (G * B))(*[p._h for p in pts])
-    _check(_lib.fhs_bsgs_inner_products_device(ctx._h, bb, G, pp, B, _vp(int(dst_ptr))), "bsgs_inner_products_to_device")
+    _check(_lib.fhs_bsgs_inner_products_device(ctx._h, _handles(ct_baby[:G], G), G, _handles(pts), B, _vp(int(dst_ptr))),
+           "bsgs_inner_products_to_device")
 
 
 def bsgs_giant_steps_from_device(ctx, src_ptr, k, chain_index, scale, elts, gk):
@@ -1026,9 +1027,8 @@ def bsgs_giant_steps(ctx, inners, elts, gk):
     k = len(inners)
     if k != len(elts) or k < 1:
         raise ValueError(f"bsgs_giant_steps: {k} inner products for {len(elts)} Galois elements")
-    hh = (_vp * k)(*[c._h for c in inners])
     e, ep = _u64_arr(elts)
-    return _ct(ctx, _lib.fhs_bsgs_giant_steps, hh, k, ep, gk._h, what="bsgs_giant_steps")
+    return _ct(ctx, _lib.fhs_bsgs_giant_steps, _handles(inners), k, ep, gk._h, what="bsgs_giant_steps")
 
 
 # ------------------------------------------------------------------ encrypted retrieval scores
@@ -1049,12 +1049,11 @@ def dot_product_many(ctx, query, chunks, rk=None, rescale=True):
     (fhs_dot_product_many).  chunks: C sequences of J = len(query) ciphertexts.  rk=None keeps the 3-component
     sums; rescale=False keeps the product scale and the level.  The C results share one device block."""
     J, Cn = _chunk_rows("dot_product_many", query, chunks)
-    qq = (_vp * J)(*[c._h for c in query])
-    dd = (_vp * (J * Cn))(*[c._h for row in chunks for c in row])
+    qq, dd = _handles(query), _handles([c for row in chunks for c in row])
     hs = (_vp * Cn)()
     _check(_lib.fhs_dot_product_many(ctx._h, qq, J, dd, Cn, None if rk is None else rk._h, 1 if rescale else 0, hs),
            "dot_product_many")
-    return [ciphertext(ctx, _vp(hs[c])) for c in range(Cn)]
+    return _ct_list(ctx, hs, Cn)
 
 
 def multiply_relin_many(ctx, a, b, rk, rescale=True):
@@ -1065,17 +1064,17 @@ def multiply_relin_many(ctx, a, b, rk, rescale=True):
     level.  The inputs share one chain index, their scales may differ.  The results share one device block."""
     a = list(a)
     n = len(a)
-    aa = (_vp * max(n, 1))(*[c._h for c in a])
+    aa = _handles(a, max(n, 1))
     bb = None
     if b is not None:
         b = list(b)
         if len(b) != n:
             raise ValueError(f"multiply_relin_many: lists of different length ({n} and {len(b)})")
-        bb = (_vp * max(n, 1))(*[c._h for c in b])
+        bb = _handles(b, max(n, 1))
     outs = (_vp * max(n, 1))()
     _check(_lib.fhs_multiply_relin_many(ctx._h, aa, bb, n, None if rk is None else rk._h, 1 if rescale else 0, outs),
            "multiply_relin_many")
-    return [ciphertext(ctx, _vp(outs[i])) for i in range(n)]
+    return _ct_list(ctx, outs, n)
 
 
 def weighted_sums(ctx, cts, W, scale):
@@ -1089,11 +1088,11 @@ def weighted_sums(ctx, cts, W, scale):
     if W.ndim != 2 or W.shape[0] != len(cts):
         raise ValueError(f"weighted_sums: W must be an (F, E) array with F = {len(cts)} rows, got shape {W.shape}")
     F, E = W.shape
-    ins = (_vp * max(F, 1))(*[c._h for c in cts])
+    ins = _handles(cts, max(F, 1))
     outs = (_vp * max(E, 1))()
     buf = W if W.size else np.zeros(1)               # an empty array may have no address: F, E are what is wrong
     _check(_lib.fhs_weighted_sums(ctx._h, ins, F, buf.ctypes.data_as(_dblp), E, E, float(scale), outs), "weighted_sums")
-    return [ciphertext(ctx, _vp(outs[i])) for i in range(E)]
+    return _ct_list(ctx, outs, E)
 
 
 def weighted_sum(ctx, cts, weights, scale):
@@ -1125,11 +1124,9 @@ def linear_transform(ctx, ct_baby, pts, G, giant_elts, gk, rescale=True):
     [rescale]( sum_g galois_{giant_elts[g]}( sum_b baby[b] * pts[g G + b] ) ), giant_elts[0] = 1."""
     G, B = int(G), len(giant_elts)
     D = len(pts)
-    bb = (_vp * G)(*[c._h for c in ct_baby[:G]])
-    pp = (_vp * D)(*[p._h for p in pts])
     e, ep = _u64_arr(giant_elts)
-    return _ct(ctx, _lib.fhs_linear_transform, bb, G, pp, D, B, ep, gk._h, 1 if rescale else 0,
-               what="linear_transform")
+    return _ct(ctx, _lib.fhs_linear_transform, _handles(ct_baby[:G], G), G, _handles(pts), D, B, ep, gk._h,
+               1 if rescale else 0, what="linear_transform")
 
 
 def multiply_const(ctx, a, value, const_scale=1.0):
@@ -1184,7 +1181,7 @@ def offload_plaintexts(pts):
     data = raw.view(_HostPlaintexts)
     data._buf = buf
     data._ctx = ctx
-    hs = (_vp * len(pts))(*[p._h for p in pts])
+    hs = _handles(pts)
     _check(_lib.fhs_offload_plaintexts(ctx._h, hs, len(pts), raw.ctypes.data_as(_u64p)), "offload_plaintexts")
     return data, ci, sc, l, ctx.N
 
@@ -1232,8 +1229,7 @@ def bsgs_from_cpu(ctx, ct_baby, data, chain_index, scale, coeff_modulus_size, po
     """bg:449: BSGS with the diagonals streamed from host memory."""
     G, B, D = int(G), int(B), int(D)
     a = _host_diagonals(ctx, data, chain_index, coeff_modulus_size, poly_modulus_degree, D, "bsgs_from_cpu")
-    bb = (_vp * G)(*[c._h for c in ct_baby[:G]])
-    return _ct(ctx, _lib.fhs_bsgs_from_cpu, bb, G, a.ctypes.data_as(_u64p), D, B, int(chain_index), float(scale),
+    return _ct(ctx, _lib.fhs_bsgs_from_cpu, _handles(ct_baby[:G], G), G, a.ctypes.data_as(_u64p), D, B, int(chain_index), float(scale),
                gk._h, what="bsgs_from_cpu")
 
 

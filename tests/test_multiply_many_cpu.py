@@ -45,7 +45,8 @@ def test_lists_of_different_length_are_rejected_in_the_binding():
 def test_validation_and_chunk_plan_under_sanitizers(tmp_path):
     """For every N = 256..32768, level 1..12, P = 1 and 3 and n = 1..5000, with the per-item scratch the host layer
     charges: the chunks cover [0, n) exactly once, their sizes differ by at most one, none exceeds the item buffer,
-    none exceeds the byte cap unless it is a single item, and no fewer chunks would fit; the null, n, component,
+    none exceeds the byte cap unless it is a single item, and no fewer chunks would fit; batch_chunks keeps the chunk
+    count and the largest chunk of the plan fhs_inner_sum_many used to make by hand (n = 1..1100); the null, n, component,
     chain-index and last-level rejections each carry their own message and status class."""
     exe = tmp_path / "multiply_many_check"
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
@@ -56,3 +57,4 @@ def test_validation_and_chunk_plan_under_sanitizers(tmp_path):
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("N=")]
     assert [int(ln.split()[0][2:]) for ln in lines] == [256 << k for k in range(8)]
     assert all(" ok: " in ln for ln in lines)
+    assert "inner_sum_many ok: 7700 plans" in r.stdout

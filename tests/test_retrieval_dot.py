@@ -8,6 +8,8 @@ P = 3 (chain "b").  The committed fixture tests/golden/retrieval_ctct_n512.npz (
 on the oracle, tests/golden/make_retrieval_golden.py) is replayed: the per-op loop must reproduce the recorded
 score ciphertexts limb for limb, and the fused scores must decode as accurately as the recorded loop did.
 Every test here needs an MI355X: -m gpu."""
+import ctypes as C
+import gc
 import json
 from pathlib import Path
 
@@ -21,6 +23,8 @@ WAVES = 8                     # FHS_DOT_WAVES: waves of a k_dot_tensor workgroup
 SCALE = 2.0 ** 40
 CHAINS = {"a": (1024, (60, 40, 40, 60), 1), "b": (1024, (59,) * 12, 3)}
 SEED = 4242
+OK, INVALID, OOM, LEVEL, SCALE_ERR = 0, 1, 2, 4, 5     # fhs_status
+_SENTINEL = 0xDEAD0
 
 
 @pytest.fixture(scope="module")
@@ -269,6 +273,76 @@ def test_error_contract(env):
     assert ph.dot_product_many(ctx, last[:2], [last[2:]], e.rk, rescale=False)[0].chain_index() == 3
     a = [e.rand(rng, 2, 3) for _ in range(2)]
     e.check(a, [[e.rand(rng, 2, 3) for _ in range(2)]], what="after the failures")
+
+
+def _raw(e, q, chunks, rk, rescale):
+    """The C call itself: (status, the output array as Python ints), the array pre-filled with a sentinel."""
+    J, Cn = len(q), len(chunks)
+    qq = (C.c_void_p * J)(*[c._h for c in q])
+    dd = (C.c_void_p * (J * Cn))(*[c._h for row in chunks for c in row])
+    out = (C.c_void_p * Cn)(*([_SENTINEL] * Cn))
+    rc = e.ph._lib.fhs_dot_product_many(e.ctx._h, qq, J, dd, Cn, rk._h if rk is not None else None, rescale, out)
+    return rc, [int(v or 0) for v in out]
+
+
+@pytest.mark.parametrize("Cn", [1, 2])
+@pytest.mark.parametrize("relin,rescale", [(True, 1), (False, 0)])
+def test_every_allocation_failing_once(env, Cn, relin, rescale):
+    """fhs_debug_fail_alloc at each of the first 16 allocations of a warm call (J = 2): a failing call is "out of
+    memory", leaves nothing allocated and every slot of `outs` as it was (include/fhespear.h: on failure outs is
+    untouched); a call the armed failure does not reach gives the oracle's limbs.  At least one k fails."""
+    e = env("a")
+    ph = e.ph
+    rng = np.random.default_rng(410 + Cn)
+    q = [e.rand(rng, 2, 3) for _ in range(2)]
+    rows = [[e.rand(rng, 2, 3) for _ in range(2)] for _ in range(Cn)]
+    Q, D = [e.up(a) for a in q], [[e.up(b) for b in row] for row in rows]
+    rk = e.rk if relin else None
+    want = [e.want(q, row, relin, bool(rescale)) for row in rows]
+    warm = ph.dot_product_many(e.ctx, Q, D, rk, bool(rescale))
+    assert all(np.array_equal(g.to_numpy(), w) for g, w in zip(warm, want))
+    del warm
+    gc.collect()
+    e.ctx.synchronize()
+    before = e.ctx.memory_in_use()
+    failed = 0
+    for k in range(16):
+        ph.debug_fail_alloc(e.ctx, k)
+        rc, outs = _raw(e, Q, D, rk, rescale)
+        pending = ph.debug_fail_alloc(e.ctx, -1)
+        if rc != OK:
+            failed += 1
+            assert rc == OOM and "out of memory" in ph._lib.fhs_last_error().decode() and not pending, k
+            assert outs == [_SENTINEL] * Cn, k
+            e.ctx.synchronize()
+            assert e.ctx.memory_in_use() == before, f"allocation {k} failed: {e.ctx.memory_in_use() - before} bytes left"
+            rc, outs = _raw(e, Q, D, rk, rescale)        # the next call
+        assert rc == OK and _SENTINEL not in outs, k
+        got = [ph.ciphertext(e.ctx, C.c_void_p(h)) for h in outs]
+        assert all(np.array_equal(g.to_numpy(), w) for g, w in zip(got, want)), k
+        del got
+        gc.collect()
+    assert failed >= 1, "a warm call allocates its results' block at least"
+
+
+def test_argument_errors_leave_outs_untouched(env):
+    """The raw call with a 3-component input, a chain-index mismatch and a scale mismatch: the status codes behind
+    test_error_contract's messages, and `outs` still holds the sentinel in every slot."""
+    e = env("a")
+    rng = np.random.default_rng(4)
+    q = [e.up(e.rand(rng, 2, 3)) for _ in range(2)]
+    row = [e.up(e.rand(rng, 2, 3)) for _ in range(2)]
+    low, three = e.up(e.rand(rng, 2, 2)), e.up(e.rand(rng, 3, 3))
+    other_scale = e.up(e.rand(rng, 2, 3), 2.0 ** 30)
+    err = lambda: e.ph._lib.fhs_last_error().decode()   # noqa: E731
+    for bad, code, word in [(three, INVALID, "2-component"), (low, LEVEL, "different chain indices"),
+                            (other_scale, SCALE_ERR, "scale mismatch")]:
+        for rk, rescale in [(e.rk, 1), (None, 0)]:
+            assert _raw(e, q, [row, [row[0], bad]], rk, rescale) == (code, [_SENTINEL] * 2) and word in err(), word
+    assert _raw(e, [q[0], other_scale], [row], e.rk, 1) == (SCALE_ERR, [_SENTINEL]) and "scale mismatch" in err()
+    rc, outs = _raw(e, q, [row], e.rk, 1)
+    assert rc == OK and outs != [_SENTINEL]
+    e.ph.ciphertext(e.ctx, C.c_void_p(outs[0]))          # owned, so destroyed
 
 
 # ---------------------------------------------------------------- the reference's search, replayed

@@ -70,10 +70,10 @@ int main() {
                 check_plan(n, N, kMulManyCap, what);
                 if (n > 64 && n % 97) continue;   // the validation at every small n and a stride of the large ones
                 for (const int* pc : {(const int*)pci.data(), (const int*)nullptr}) {
-                    bool level = l >= 2;
-                    const char* err = mulp_rescale_many_error(false, n, two.data(), ci.data(), pc, L0, &level);
-                    if (l >= 2) REQUIRE(!err && !level, "%s n=%d: rejected \"%s\"", what, n, err ? err : "");
-                    else REQUIRE(err && strstr(err, "no level left") && level, "%s n=%d: last level \"%s\"", what, n, err ? err : "accepted");
+                    ArgErr cls = l >= 2 ? ARG_LEVEL : ARG_INVALID;
+                    const char* err = mulp_rescale_many_error(false, n, two.data(), ci.data(), pc, L0, &cls);
+                    if (l >= 2) REQUIRE(!err && cls == ARG_INVALID, "%s n=%d: rejected \"%s\"", what, n, err ? err : "");
+                    else REQUIRE(err && strstr(err, "no level left") && cls == ARG_LEVEL, "%s n=%d: last level \"%s\"", what, n, err ? err : "accepted");
                 }
             }
         }
@@ -124,15 +124,15 @@ int main() {
                        {false, 3, c2, ci_bad, ci_bad, true, "chain index out of range"},
                        {false, 3, c2, ci_zero, nullptr, true, "chain index out of range"}};
     for (const Bad& b : bad) {
-        bool level = !b.level;
-        const char* err = mulp_rescale_many_error(b.null_arg, b.n, b.ncomp, b.ci, b.pci, L3, &level);
-        REQUIRE(err && strstr(err, b.word) && level == b.level, "n=%d \"%s\": \"%s\", level %d", b.n, b.word,
-                err ? err : "accepted", level);
+        ArgErr cls = b.level ? ARG_INVALID : ARG_LEVEL;
+        const char* err = mulp_rescale_many_error(b.null_arg, b.n, b.ncomp, b.ci, b.pci, L3, &cls);
+        REQUIRE(err && strstr(err, b.word) && cls == (b.level ? ARG_LEVEL : ARG_INVALID), "n=%d \"%s\": \"%s\", class %d", b.n,
+                b.word, err ? err : "accepted", (int)cls);
     }
     for (const int* pc : {ci1, (const int*)nullptr})
         for (int n : {1, 3}) {
-            bool level = true;
-            REQUIRE(mulp_rescale_many_error(false, n, c2, ci1, pc, L3, &level) == nullptr && !level, "accepted call");
+            ArgErr cls = ARG_LEVEL;
+            REQUIRE(mulp_rescale_many_error(false, n, c2, ci1, pc, L3, &cls) == nullptr && cls == ARG_INVALID, "accepted call");
         }
     printf("OK\n");
     return 0;

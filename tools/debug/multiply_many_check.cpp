@@ -9,7 +9,8 @@
 // and every n = 1..5000 (all stages, exact convention; the other stage sets at n = 1..64, around every chunk-count
 // boundary up to 8 chunks, and at 4999 and 5000): the chunks cover [0, n) exactly once in order, their sizes differ by at most one, none has
 // more than kKsMaxItems items, none costs more than kMulManyCap bytes unless it is a single item, and no plan with
-// fewer chunks would fit.  Then the rejections: null, n, component count, chain index and the last level each carry
+// fewer chunks would fit.  Then fhs_inner_sum_many's former plan, written out, against batch_chunks for n = 1..1100 and
+// seven chunk bounds: the same chunk count and the same largest chunk.  Then the rejections: null, n, component count, chain index and the last level each carry
 // their own message and status class.  Prints one line per N, then OK; exits non-zero at the first violation.
 #include <cstdio>
 #include <cstdlib>
@@ -102,6 +103,21 @@ int main() {
         REQUIRE((size_t)ch[0].second * item <= kMulManyCap && ch[0].second == 24, "fri: %d pairs per chunk, %zu bytes each",
                 ch[0].second, item);
     }
+    // fhs_inner_sum_many's former hand-rolled plan (rmax items at most per chunk, nchunks = ceil(n / rmax), steps of
+    // rchunk = ceil(n / nchunks)): batch_chunks gives the same chunk count and the same largest (first) chunk, so the
+    // key-switch workspace, sized by that chunk, is what it was
+    int former = 0;
+    for (int rmax : {1, 2, 3, 4, 31, 32, 512})
+        for (int n = 1; n <= 1100; ++n, ++former) {
+            const int nchunks = (n + rmax - 1) / rmax, rchunk = (n + nchunks - 1) / nchunks;
+            const auto ch = batch_chunks(n, 8, rmax, (size_t)8 * 512);          // bound by the item buffer
+            const auto cb = batch_chunks(n, 8, kKsMaxItems, (size_t)8 * rmax);   // bound by the bytes
+            REQUIRE((int)ch.size() == nchunks && ch[0].second == rchunk, "n=%d rmax=%d: %zu chunks, first of %d", n, rmax,
+                    ch.size(), ch[0].second);
+            REQUIRE((int)cb.size() == nchunks && cb[0].second == rchunk, "n=%d rmax=%d (bytes): %zu chunks, first of %d", n, rmax,
+                    cb.size(), cb[0].second);
+        }
+    printf("inner_sum_many ok: %d plans keep their chunk count and largest chunk\n", former);
     // the rejections, each with its own message and status class
     const int L0 = 3;
     const int two[4] = {2, 2, 2, 2}, three[4] = {2, 2, 3, 2}, ci1[4] = {1, 1, 1, 1}, ci_mixed[4] = {1, 1, 1, 2},
@@ -127,19 +143,19 @@ int main() {
                        {false, 2, two, ci_last, 4, 1, true, "rescale_to_next: no level left"},
                        {false, 2, two, ci_bad, 4, 0, true, "chain index out of range"}};
     for (const Bad& b : bad) {
-        bool level = !b.level;
-        const char* err = multiply_many_error(b.null_arg, b.n, b.ncomp, b.ci, b.count, L0, b.rescale, &level);
-        REQUIRE(err && strstr(err, b.word) && level == b.level, "n=%d \"%s\": \"%s\", level %d", b.n, b.word,
-                err ? err : "accepted", level);
+        ArgErr cls = b.level ? ARG_INVALID : ARG_LEVEL;
+        const char* err = multiply_many_error(b.null_arg, b.n, b.ncomp, b.ci, b.count, L0, b.rescale, &cls);
+        REQUIRE(err && strstr(err, b.word) && cls == (b.level ? ARG_LEVEL : ARG_INVALID), "n=%d \"%s\": \"%s\", class %d", b.n,
+                b.word, err ? err : "accepted", (int)cls);
     }
     for (int rescale = 0; rescale < 2; ++rescale)
         for (size_t count : {(size_t)2, (size_t)4}) {
-            bool level = true;
-            REQUIRE(multiply_many_error(false, 2, two, ci1, count, L0, rescale, &level) == nullptr && !level, "accepted call");
+            ArgErr cls = ARG_LEVEL;
+            REQUIRE(multiply_many_error(false, 2, two, ci1, count, L0, rescale, &cls) == nullptr && cls == ARG_INVALID, "accepted call");
         }
     {   // the last level without rescale is a legal call
-        bool level = true;
-        REQUIRE(multiply_many_error(false, 2, two, ci_last, 4, L0, 0, &level) == nullptr && !level, "last level, no rescale");
+        ArgErr cls = ARG_LEVEL;
+        REQUIRE(multiply_many_error(false, 2, two, ci_last, 4, L0, 0, &cls) == nullptr && cls == ARG_INVALID, "last level, no rescale");
     }
     printf("OK\n");
     return 0;

@@ -73,32 +73,32 @@ static void check_errors() {
         double scale;
         const int *ncomp, *ci;
         const double* scales;
-        WsumErr cls;
+        ArgErr cls;
         const char* word;
     };
-    const Bad bad[] = {{true, 3, 2, 2, 2.0, two, ci1, sc, WSUM_INVALID, "null argument"},
-                       {false, 0, 2, 2, 2.0, two, ci1, sc, WSUM_INVALID, "1 <= F <= 4096"},
-                       {false, -1, 2, 2, 2.0, two, ci1, sc, WSUM_INVALID, "1 <= F <= 4096"},
-                       {false, 4097, 2, 2, 2.0, two, ci1, sc, WSUM_INVALID, "1 <= F <= 4096"},
-                       {false, 3, 0, 2, 2.0, two, ci1, sc, WSUM_INVALID, "E >= 1"},
-                       {false, 3, 2, 1, 2.0, two, ci1, sc, WSUM_INVALID, "ldw >= E"},
-                       {false, 3, 2, 2, 0.0, two, ci1, sc, WSUM_INVALID, "bad scale"},
-                       {false, 3, 2, 2, -4.0, two, ci1, sc, WSUM_INVALID, "bad scale"},
-                       {false, 3, 2, 2, inf, two, ci1, sc, WSUM_INVALID, "bad scale"},
-                       {false, 3, 2, 2, nan, two, ci1, sc, WSUM_INVALID, "bad scale"},
-                       {false, 3, 2, 2, 2.0, nullptr, ci1, sc, WSUM_INVALID, "null argument"},
-                       {false, 3, 2, 2, 2.0, three, ci_mixed, sc_bad, WSUM_INVALID, "2-component"},
-                       {false, 3, 2, 2, 2.0, two, ci_mixed, sc_bad, WSUM_LEVEL, "share one chain index"},
-                       {false, 3, 2, 2, 2.0, two, ci_bad, sc, WSUM_LEVEL, "chain index out of range"},
-                       {false, 3, 2, 2, 2.0, two, ci_last, sc_bad, WSUM_LEVEL, "no level left"},
-                       {false, 3, 2, 2, 2.0, two, ci1, sc_bad, WSUM_SCALE, "scale mismatch"}};
+    const Bad bad[] = {{true, 3, 2, 2, 2.0, two, ci1, sc, ARG_INVALID, "null argument"},
+                       {false, 0, 2, 2, 2.0, two, ci1, sc, ARG_INVALID, "1 <= F <= 4096"},
+                       {false, -1, 2, 2, 2.0, two, ci1, sc, ARG_INVALID, "1 <= F <= 4096"},
+                       {false, 4097, 2, 2, 2.0, two, ci1, sc, ARG_INVALID, "1 <= F <= 4096"},
+                       {false, 3, 0, 2, 2.0, two, ci1, sc, ARG_INVALID, "E >= 1"},
+                       {false, 3, 2, 1, 2.0, two, ci1, sc, ARG_INVALID, "ldw >= E"},
+                       {false, 3, 2, 2, 0.0, two, ci1, sc, ARG_INVALID, "bad scale"},
+                       {false, 3, 2, 2, -4.0, two, ci1, sc, ARG_INVALID, "bad scale"},
+                       {false, 3, 2, 2, inf, two, ci1, sc, ARG_INVALID, "bad scale"},
+                       {false, 3, 2, 2, nan, two, ci1, sc, ARG_INVALID, "bad scale"},
+                       {false, 3, 2, 2, 2.0, nullptr, ci1, sc, ARG_INVALID, "null argument"},
+                       {false, 3, 2, 2, 2.0, three, ci_mixed, sc_bad, ARG_INVALID, "2-component"},
+                       {false, 3, 2, 2, 2.0, two, ci_mixed, sc_bad, ARG_LEVEL, "share one chain index"},
+                       {false, 3, 2, 2, 2.0, two, ci_bad, sc, ARG_LEVEL, "chain index out of range"},
+                       {false, 3, 2, 2, 2.0, two, ci_last, sc_bad, ARG_LEVEL, "no level left"},
+                       {false, 3, 2, 2, 2.0, two, ci1, sc_bad, ARG_SCALE, "scale mismatch"}};
     for (const Bad& b : bad) {
-        WsumErr cls = b.cls == WSUM_INVALID ? WSUM_LEVEL : WSUM_INVALID;
+        ArgErr cls = b.cls == ARG_INVALID ? ARG_LEVEL : ARG_INVALID;
         const char* err = weighted_sums_error(b.null_arg, b.F, b.E, b.ldw, b.scale, b.ncomp, b.ci, b.scales, L0, &cls);
         REQUIRE(err && strstr(err, b.word) && cls == b.cls, "\"%s\": \"%s\", class %d", b.word, err ? err : "accepted", (int)cls);
     }
-    WsumErr cls = WSUM_LEVEL;
-    REQUIRE(!weighted_sums_error(false, 3, 2, 5, 2.0, two, ci1, sc, L0, &cls) && cls == WSUM_INVALID, "accepted call");
+    ArgErr cls = ARG_LEVEL;
+    REQUIRE(!weighted_sums_error(false, 3, 2, 5, 2.0, two, ci1, sc, L0, &cls) && cls == ARG_INVALID, "accepted call");
     REQUIRE(!weighted_sums_error(false, 1, 1, 1, 1e-3, two, ci1, sc, L0, &cls), "F = E = 1");
     // the weights
     const std::vector<uint64_t> q = ntt_primes(40, 2, 256);
